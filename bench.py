@@ -19,14 +19,30 @@ the "data" field).  ``--transport local`` measures the loopback
 transport for comparison.  The reference publishes no numbers
 (BASELINE.md): vs_baseline is null.
 
-With one rank on a GPU box the main (noop) line also carries a
-"secondary" list: short runs of the mm and staging configs
-(BASELINE.json configs 2 and 4) so a single driver invocation observes
-GPU-work dispatch, not only no-ops.
+A plain run does only what the headline figure needs: set up, warm up,
+time ``--steps`` steps, print one JSON line.  With ``--full`` and one
+rank on a GPU box the main (noop) line also carries a "secondary" list:
+short runs of the mm and staging configs (BASELINE.json configs 2 and 4)
+so a single invocation observes GPU-work dispatch, not only no-ops.
+
+On a GPU box a run loads the in-tree CDNA4 library in this process and
+lets it count the devices (no GPU work): the workers' GPU path needs it,
+and a run without it is an error, not a figure for a reduced pipeline.
+
+``--dump-outputs DIR`` writes what the caller of the last timed step
+received as ``DIR/<name>.npy`` (float32/float64, at most 64 MB in all; a
+larger array is cut to a fixed seeded sample): ``result`` is the
+electron's return value, ``worker_gpu`` and ``worker_served`` come from
+the task record (see caller_view).  Electrons that draw
+random inputs are seeded in that mode, so two builds can be compared
+output for output.
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
         [--config noop|noop-stub|mm|staging|fan|rccl]
-        [--transport sshim|local] [--no-secondary]
+        [--transport sshim|local] [--full [--no-secondary]]
+        [--dump-outputs DIR]
+(--no-secondary only matters with --full; without it there are no
+secondary runs to skip.)
 """
 
 from __future__ import annotations
@@ -55,9 +71,10 @@ SSHIM_PASS_ENV = (
 )
 
 
-def build_electron(config: str):
+def build_electron(config: str, seed=None):
     """Electron bodies are defined inside a factory so cloudpickle
-    serializes them by value."""
+    serializes them by value.  ``seed`` (set with --dump-outputs) pins
+    the inputs of electrons that draw random ones."""
     if config in ("noop", "noop-stub", "noop-isolated", "fan"):
 
         def noop():
@@ -67,16 +84,18 @@ def build_electron(config: str):
 
     if config == "mm":
         # BASELINE config 2: single torch.mm(4096x4096, bf16) on one MI355X
-        def mm_electron(n=4096):
+        def mm_electron(n=4096, seed=None):
             import torch
 
+            if seed is not None:
+                torch.manual_seed(seed)
             a = torch.randn(n, n, device="cuda", dtype=torch.bfloat16)
             b = torch.randn(n, n, device="cuda", dtype=torch.bfloat16)
             c = a @ b
             torch.cuda.synchronize()
             return float(c.float().mean().item())
 
-        return mm_electron, [], {}
+        return mm_electron, [], ({} if seed is None else {"seed": seed})
 
     if config == "staging":
         # BASELINE config 4: 1 GB tensor return through pinned staging
@@ -148,12 +167,15 @@ async def bench_once(
     local_rank: int,
     has_cuda: bool,
     gpu_count: int,
+    seed=None,
 ) -> dict:
     """Run one config through the executor; returns elapsed/latencies/
-    warm-path phase means (warmup records excluded)."""
+    warm-path phase means (warmup records excluded) and what the last
+    step handed back to its caller."""
     from covalent_ssh_plugin_amd import SSHExecutor
 
-    fn, fargs, fkwargs = build_electron(config)
+    fn, fargs, fkwargs = build_electron(config, seed)
+    last = {"result": None}
     ex = SSHExecutor(
         cache_dir=cache_dir,
         python_path=sys.executable,
@@ -180,11 +202,12 @@ async def bench_once(
     )
 
     async def one_step() -> float:
+        last["result"] = None  # drop the previous step's result first
         t0 = time.perf_counter()
         if config == "fan":
             # BASELINE config 3: a fan of no-op electrons spread
             # round-robin across the node's GPU slots
-            await asyncio.gather(
+            last["result"] = await asyncio.gather(
                 *[
                     ex.execute(fn, list(fargs), dict(fkwargs),
                                dispatch_id=f"bench{rank}", node_id=i)
@@ -192,7 +215,7 @@ async def bench_once(
                 ]
             )
         else:
-            await ex.execute(
+            last["result"] = await ex.execute(
                 fn, list(fargs), dict(fkwargs),
                 dispatch_id=f"bench{rank}", node_id=0,
             )
@@ -212,7 +235,104 @@ async def bench_once(
     phase_means = summarize(ex.task_records[n_warm_records:]).get(
         "phase_mean_ms", {}
     )
-    return {"elapsed": elapsed, "latencies": lat, "phases": phase_means}
+    record = ex.last_task_record
+    return {"elapsed": elapsed, "latencies": lat, "phases": phase_means,
+            "last_result": last["result"],
+            "last_meta": (record.remote_meta if record else None) or {}}
+
+
+# .npy payload budget for --dump-outputs: under 64 MB with room for headers
+DUMP_LIMIT_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def _named_leaves(value, name):
+    """Flatten an electron's return value into (name, leaf) pairs, a leaf
+    being a CPU tensor or a float64 ndarray: dicts and sequences that
+    hold tensors recurse, numeric scalars/sequences become arrays;
+    non-numeric leaves (strings, None) carry nothing to compare and are
+    left out."""
+    import numpy as np
+    import torch
+
+    if isinstance(value, torch.Tensor):
+        yield name, value.detach().cpu()
+    elif isinstance(value, dict):
+        for k in sorted(value, key=str):
+            yield from _named_leaves(value[k], f"{name}_{k}")
+    elif isinstance(value, (list, tuple)) and any(
+        isinstance(v, (torch.Tensor, dict, list, tuple)) for v in value
+    ):
+        for i, v in enumerate(value):
+            yield from _named_leaves(v, f"{name}_{i}")
+    elif isinstance(value, (bool, int, float, np.number, np.ndarray, list, tuple)):
+        try:
+            yield name, np.asarray(value, dtype=np.float64)
+        except (TypeError, ValueError):
+            pass
+
+
+# Device properties the remote side's CDNA4 library probe reports with
+# every task: fixed for a given GPU, unlike its measured bandwidth/TFLOPs.
+WORKER_GPU_PROPS = ("cu_count", "max_clock_mhz", "lds_per_cu_kb", "wavefront_size")
+
+
+def caller_view(result, remote_meta: dict) -> dict:
+    """What the caller of the last timed step received, by output name:
+    the electron's return value and, from the task record the executor
+    keeps for it, the run-to-run stable part of the remote side's report
+    — the device properties read by the CDNA4 library on the worker's
+    pinned GPU and the number of electrons that worker had served (one
+    warm worker serving every step gives warmup + steps).
+
+    The two worker_* outputs are not numerics of the electron.  They say
+    that the same remote path ran: ``worker_gpu`` that the worker's
+    native probe saw the same device, ``worker_served`` that one warm
+    worker took every electron.  A worker respawned mid-run (a transport
+    event, e.g. a dropped channel) lowers ``worker_served``; read a
+    difference there as that, not as a numerical change between builds."""
+    gpu = remote_meta.get("gpu") or {}
+    return {
+        "result": result,
+        "worker_gpu": [gpu[k] for k in WORKER_GPU_PROPS] if gpu else None,
+        "worker_served": remote_meta.get("served"),
+    }
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> list:
+    """Write ``outputs`` (name -> value) as ``<name>.npy`` files in
+    float32/float64, at most DUMP_LIMIT_BYTES in all.  A leaf over
+    its share of the budget is cut to a fixed sample of its elements
+    (seeded, distinct indices in ascending order, so the sample keeps
+    the leaf's order)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    leaves = [
+        leaf for name in sorted(outputs)
+        for leaf in _named_leaves(outputs[name], name)
+    ]
+    share = DUMP_LIMIT_BYTES // max(1, len(leaves))
+    written = []
+    for name, leaf in leaves:
+        is_tensor = isinstance(leaf, torch.Tensor)
+        wide = not is_tensor or leaf.dtype in (torch.float64, torch.int64)
+        size = leaf.numel() if is_tensor else leaf.size
+        keep = share // (8 if wide else 4)
+        if size > keep:
+            # one seeded pick from each of `keep` equal strata: distinct,
+            # ascending, spread over the whole leaf, O(keep) to draw
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            starts = np.arange(keep, dtype=np.int64) * size // keep
+            idx = starts + rng.integers(0, size // keep, size=keep)
+            leaf = leaf.reshape(-1)[torch.from_numpy(idx) if is_tensor else idx]
+        if is_tensor:
+            leaf = leaf.to(torch.float64 if wide else torch.float32).numpy()
+        path = os.path.join(out_dir, f"{name}.npy")
+        np.save(path, leaf)
+        written.append(path)
+    return written
 
 
 def main() -> None:
@@ -226,8 +346,15 @@ def main() -> None:
         help="sshim: real OpenSSH transport via the PATH-shim ssh client "
              "(default); local: loopback transport",
     )
+    parser.add_argument("--full", action="store_true",
+                        help="after the timed steps also run everything "
+                             "beside the headline figure (the secondary "
+                             "mm/staging GPU runs)")
     parser.add_argument("--no-secondary", action="store_true",
-                        help="skip the secondary mm/staging GPU runs")
+                        help="with --full: skip the secondary mm/staging GPU runs")
+    parser.add_argument("--dump-outputs", default="", metavar="DIR",
+                        help="write what the last timed step returned as "
+                             "DIR/<name>.npy (rank 0)")
     parser.add_argument("--dump-latencies", default="",
                         help="write per-step latencies (seconds, one per line)")
     parser.add_argument("--fan", type=int, default=64,
@@ -237,6 +364,8 @@ def main() -> None:
         args.steps = default_steps(args.config)
     if args.warmup is None:
         args.warmup = default_warmup(args.config)
+    if args.steps < 1 or args.warmup < 0:
+        parser.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -262,6 +391,20 @@ def main() -> None:
             # modulo: degenerate topologies (more ranks than GPUs, gloo
             # fallback) must not address nonexistent devices
             torch.cuda.set_device(local_rank % max(1, gpu_count))
+
+    def require_gpu_library():
+        """The workers' GPU prologue and pinned staging come from the
+        in-tree CDNA4 library.  Without it the executor only logs a
+        warning and dispatches all the same, so the figures would
+        describe a pipeline with no native code in it.  With a GPU
+        present, load the library in this process and let it count the
+        devices (no kernels, no allocations); a missing or broken
+        library raises GpuLibError instead of being measured around."""
+        if has_cuda:
+            from covalent_ssh_plugin_amd.gpu import probe as gpu_probe
+
+            if gpu_probe.device_count() < 1:
+                raise SystemExit("CDNA4 library loaded but sees no GPU")
 
     def barrier_sync():
         if distributed:
@@ -302,9 +445,12 @@ def main() -> None:
             config=args.config, steps=0, warmup=args.warmup, fan=args.fan,
             **common,
         )
+        # checked here, where this process first touches the GPU anyway
+        require_gpu_library()
         barrier_sync()
         timed = await bench_once(
             config=args.config, steps=args.steps, warmup=0, fan=args.fan,
+            seed=0 if args.dump_outputs else None,
             **common,
         )
         barrier_sync()
@@ -312,10 +458,12 @@ def main() -> None:
 
         # secondary GPU configs: driver-observed mm + staging dispatch in
         # the same invocation (VERDICT r1 "Next round" #7); single-rank
-        # GPU runs only, so the flagship timing above stays undisturbed
+        # GPU runs only, so the flagship timing above stays undisturbed.
+        # Only with --full: a plain run stops at its headline figure.
         out["secondary"] = []
         if (
-            args.config == "noop"
+            args.full
+            and args.config == "noop"
             and not args.no_secondary
             and not distributed
             and has_cuda
@@ -365,6 +513,11 @@ def main() -> None:
     if args.dump_latencies and rank == 0:
         with open(args.dump_latencies, "w") as f:
             f.write("\n".join(f"{x:.9f}" for x in timed["latencies"]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(
+            args.dump_outputs,
+            caller_view(timed["last_result"], timed["last_meta"]),
+        )
 
     total_electrons = args.steps * world_size * electrons_per_step
     eps = total_electrons / elapsed
