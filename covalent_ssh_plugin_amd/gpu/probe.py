@@ -80,6 +80,15 @@ def load(path: str = "") -> ctypes.CDLL:
     lib.csp_memcpy_d2h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     lib.csp_memcpy_h2d.restype = ctypes.c_int
     lib.csp_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    lib.csp_d2h_stream_fd.restype = ctypes.c_int
+    lib.csp_d2h_stream_fd.argtypes = [
+        ctypes.c_int,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_double),
+    ]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -137,6 +146,29 @@ def mem_info(device: int = 0) -> dict:
 def warmup(device: int = 0, budget_ms: int = 50) -> None:
     lib = load()
     _check(lib, lib.csp_warmup(device, budget_ms), "csp_warmup")
+
+
+# csp_d2h_stream_fd return codes
+STREAM_OK = 0
+STREAM_FAILED_BEFORE_HEADER = 1
+STREAM_FAILED_MID_FRAME = 2
+
+
+def stream_d2h_to_fd(fd: int, data_ptr: int, nbytes: int, chunk_bytes: int = 0) -> dict:
+    """Frame ``nbytes`` at device pointer ``data_ptr`` onto ``fd`` (8-byte
+    big-endian length, then the bytes), the D2H copy overlapped with the
+    writes through the two-chunk pinned ring.  ``chunk_bytes`` 0 takes the
+    library default.  Returns ``{"rc", "d2h_ms", "write_ms"}``; a non-zero
+    ``rc`` is one of the STREAM_FAILED_* codes, not an exception — the
+    caller decides what a cut-short frame means for its stream."""
+    lib = load()
+    d2h_ms = ctypes.c_double()
+    write_ms = ctypes.c_double()
+    rc = lib.csp_d2h_stream_fd(
+        fd, ctypes.c_void_p(data_ptr), nbytes, chunk_bytes,
+        ctypes.byref(d2h_ms), ctypes.byref(write_ms),
+    )
+    return {"rc": rc, "d2h_ms": d2h_ms.value, "write_ms": write_ms.value}
 
 
 def staged_d2h_bytes(data_ptr: int, nbytes: int) -> bytes:

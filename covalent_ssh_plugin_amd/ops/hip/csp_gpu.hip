@@ -13,7 +13,11 @@
 //   * csp_host_alloc / csp_host_free / csp_staging_get /
 //     csp_memcpy_d2h / csp_memcpy_h2d
 //                     — hipHostMalloc-pinned staging for large tensor
-//                       results on the SFTP/stdout return path.
+//                       results on the SFTP/stdout return path,
+//   * csp_d2h_stream_fd
+//                     — a large tensor result framed straight onto the
+//                       worker's channel fd, its D2H copy overlapped with
+//                       the pipe writes through a two-chunk pinned ring.
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -27,8 +31,11 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "../csrc/csp_io.h"  // exact-length fd writes (header-only, host code)
+
 #include <cstdio>
 #include <cstring>
+#include <ctime>
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -416,6 +423,142 @@ extern "C" int csp_memcpy_h2d(void* dst_dev, const void* src_host, size_t n) {
     HIP_TRY(hipMemcpyAsync(dst_dev, src_host, n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
+}
+
+// Return one block to the staging freelist (the streaming sender's ring;
+// csp_staging_release_all would also take back blocks other callers hold).
+static void staging_release_one(void* p) {
+    if (!p) return;
+    std::lock_guard<std::mutex> lock(g_staging_mu);
+    for (size_t i = 0; i < g_staging_in_use.size(); ++i) {
+        if (g_staging_in_use[i].first == p) {
+            g_staging_free.push_back(g_staging_in_use[i]);
+            g_staging_in_use.erase(g_staging_in_use.begin() + i);
+            return;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Streaming D2H: one length-framed buffer from device memory to an fd
+// ---------------------------------------------------------------------------
+//
+// Writes the 8-byte big-endian frame length, then the nbytes at src_dev,
+// through a ring of two pinned chunks from the staging pool: while chunk
+// i is written to fd, the copy of chunk i+1 runs on copy_stream().  The
+// D2H engine and the pipe are busy together, and the pinned footprint is
+// 2 x chunk_bytes instead of the whole tensor.
+//
+// Chunk size: sweep over 1/4/16/64 MiB in profiles/staging_return_path.md.
+static const size_t kStreamChunkDefault = size_t(16) << 20;
+static const int kStreamRing = 2;
+
+#define CSP_STREAM_OK 0
+#define CSP_STREAM_FAILED_BEFORE_HEADER 1  // no byte of this frame was written
+#define CSP_STREAM_FAILED_MID_FRAME 2      // the frame on fd is cut short
+
+static double mono_ms() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec * 1.0e3 + (double)ts.tv_nsec / 1.0e6;
+}
+
+// d2h_ms (optional): copy-engine time summed over the chunks, from events
+// around each copy.  write_ms (optional): host time spent inside write().
+extern "C" int csp_d2h_stream_fd(int fd, const void* src_dev, size_t nbytes,
+                                 size_t chunk_bytes, double* d2h_ms,
+                                 double* write_ms) {
+    if (d2h_ms) *d2h_ms = 0.0;
+    if (write_ms) *write_ms = 0.0;
+    if (chunk_bytes == 0) chunk_bytes = kStreamChunkDefault;
+    if (chunk_bytes > nbytes) chunk_bytes = nbytes;  // small payload: one short chunk
+    const size_t nchunks = nbytes ? (nbytes + chunk_bytes - 1) / chunk_bytes : 0;
+    const int ring = nchunks < (size_t)kStreamRing ? (int)nchunks : kStreamRing;
+
+    unsigned char header[8];
+    for (int i = 0; i < 8; ++i)
+        header[i] = (unsigned char)((unsigned long long)nbytes >> (8 * (7 - i)));
+
+    hipStream_t s = copy_stream();
+    void* buf[kStreamRing] = {nullptr, nullptr};
+    hipEvent_t ev_start[kStreamRing] = {nullptr, nullptr};
+    hipEvent_t ev_done[kStreamRing] = {nullptr, nullptr};
+    const char* src = static_cast<const char*>(src_dev);
+    bool header_out = false;  // any byte of the header handed to the kernel
+    bool copies_issued = false;
+    double t_d2h = 0.0, t_write = 0.0;
+    int rc = CSP_STREAM_OK;
+
+    auto fail_hip = [&](const char* what, hipError_t e) {
+        set_err(what, e);
+        rc = header_out ? CSP_STREAM_FAILED_MID_FRAME : CSP_STREAM_FAILED_BEFORE_HEADER;
+    };
+    auto fail_io = [&](const char* what, int io_rc) {
+        snprintf(g_err, sizeof(g_err), "%s: %s", what, strerror(-io_rc));
+        rc = header_out ? CSP_STREAM_FAILED_MID_FRAME : CSP_STREAM_FAILED_BEFORE_HEADER;
+    };
+    auto issue = [&](size_t i) -> bool {
+        const int slot = (int)(i % kStreamRing);
+        const size_t off = i * chunk_bytes;
+        const size_t len = std::min(chunk_bytes, nbytes - off);
+        hipError_t e = hipEventRecord(ev_start[slot], s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(buf[slot], src + off, len, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ev_done[slot], s);
+        copies_issued = true;
+        if (e != hipSuccess) { fail_hip("stream chunk copy", e); return false; }
+        return true;
+    };
+    auto timed_write = [&](const void* p, size_t n) -> bool {
+        size_t done = 0;
+        const double t0 = mono_ms();
+        int io_rc = csp_io_detail::write_full(fd, p, n, &done);
+        t_write += mono_ms() - t0;
+        if (done > 0) header_out = true;
+        if (io_rc != CSP_IO_OK) { fail_io("stream write", io_rc); return false; }
+        return true;
+    };
+
+    for (int k = 0; k < ring && rc == CSP_STREAM_OK; ++k) {
+        buf[k] = csp_staging_alloc(chunk_bytes);
+        if (!buf[k]) { rc = CSP_STREAM_FAILED_BEFORE_HEADER; break; }  // g_err set
+        hipError_t e = hipEventCreate(&ev_start[k]);
+        if (e == hipSuccess) e = hipEventCreate(&ev_done[k]);
+        if (e != hipSuccess) fail_hip("hipEventCreate", e);
+    }
+
+    // The first chunk's copy is in flight before the header goes out, so
+    // a bad source pointer fails the call before the frame has begun.
+    if (rc == CSP_STREAM_OK && nchunks > 0) issue(0);
+    if (rc == CSP_STREAM_OK && nchunks > 0) {
+        hipError_t e = hipEventSynchronize(ev_done[0]);
+        if (e != hipSuccess) fail_hip("hipEventSynchronize", e);
+    }
+    if (rc == CSP_STREAM_OK) timed_write(header, sizeof(header));
+
+    for (size_t i = 0; i < nchunks && rc == CSP_STREAM_OK; ++i) {
+        const int slot = (int)(i % kStreamRing);
+        // slot of chunk i+1 held chunk i-1, whose write has returned
+        if (i + 1 < nchunks && !issue(i + 1)) break;
+        hipError_t e = hipEventSynchronize(ev_done[slot]);
+        if (e != hipSuccess) { fail_hip("hipEventSynchronize", e); break; }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev_start[slot], ev_done[slot]) == hipSuccess)
+            t_d2h += ms;
+        const size_t off = i * chunk_bytes;
+        if (!timed_write(buf[slot], std::min(chunk_bytes, nbytes - off))) break;
+    }
+
+    // No copy may still target a ring buffer once it is back in the pool.
+    if (copies_issued && rc != CSP_STREAM_OK) (void)hipStreamSynchronize(s);
+    for (int k = 0; k < kStreamRing; ++k) {
+        if (ev_start[k]) (void)hipEventDestroy(ev_start[k]);
+        if (ev_done[k]) (void)hipEventDestroy(ev_done[k]);
+        staging_release_one(buf[k]);
+    }
+    if (d2h_ms) *d2h_ms = t_d2h;
+    if (write_ms) *write_ms = t_write;
+    return rc;
 }
 
 // On-box variant exploration for the HBM sweep (tools only; the probe

@@ -25,6 +25,11 @@ def _template_text(path: str) -> str:
 # hipHostMalloc-pinned D2H path wins (PCIe Gen5 x16 ~63 GB/s vs pageable).
 DEFAULT_STAGING_THRESHOLD = 64 * 1024 * 1024
 
+# Pinned ring chunk for streaming a CUDA result onto the worker channel
+# (csp_d2h_stream_fd); the winner of the on-box sweep in
+# profiles/staging_return_path.md.
+STREAM_CHUNK_BYTES = 16 * 1024 * 1024
+
 
 def render_stub(
     *,
@@ -75,6 +80,7 @@ def render_worker(
         "__CSP_GPU_LIB__": gpu_lib_path,
         "__CSP_WARMUP__": repr(bool(warmup)),
         "__CSP_STAGING_THRESHOLD__": str(thr),
+        "__CSP_STREAM_CHUNK__": str(STREAM_CHUNK_BYTES),
         "__CSP_IDLE_TIMEOUT__": repr(float(idle_timeout)),
         "__CSP_ISOLATE__": repr(bool(isolate)),
         "__CSP_ISOLATE_PRELOAD__": str(isolate_preload),

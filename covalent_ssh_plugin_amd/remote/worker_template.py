@@ -32,9 +32,11 @@ Protocol (all frames: 8-byte big-endian length + payload):
              followed by nbuf RAW tensor-buffer frames.  Large tensors in
              the result are replaced by ("__csp_tensor_buffer_v1__", i)
              markers and shipped out-of-band as raw frames — CUDA tensors
-             straight from the hipHostMalloc-pinned staging block, large
-             CPU tensors zero-copy from their own storage — skipping both
-             pickle copies on the payload.  meta["buffers"][i] carries
+             streamed by csp_d2h_stream_fd (their D2H copy runs chunk by
+             chunk through a small hipHostMalloc-pinned ring WHILE the
+             frame is being written), large CPU tensors zero-copy from
+             their own storage — skipping both pickle copies on the
+             payload.  meta["buffers"][i] carries
              dtype/shape.  A zero-length request frame means: shut down.
 
 The worker's REAL stdout is reserved for the protocol; fd 1 is
@@ -52,6 +54,8 @@ import time
 GPU_LIB = "__CSP_GPU_LIB__"
 DO_WARMUP = bool(__CSP_WARMUP__)
 STAGING_THRESHOLD = int(__CSP_STAGING_THRESHOLD__)
+# bytes per pinned ring chunk when a CUDA result is streamed to the channel
+STREAM_CHUNK = int(__CSP_STREAM_CHUNK__)
 IDLE_TIMEOUT = float(__CSP_IDLE_TIMEOUT__)  # seconds; 0 = never exit
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
@@ -153,6 +157,15 @@ def _load_gpu_lib():
     lib.csp_staging_release_all.restype = ctypes.c_int
     lib.csp_memcpy_d2h.restype = ctypes.c_int
     lib.csp_memcpy_d2h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    lib.csp_d2h_stream_fd.restype = ctypes.c_int
+    lib.csp_d2h_stream_fd.argtypes = [
+        ctypes.c_int,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_double),
+    ]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -204,11 +217,45 @@ def _prologue():
             )
 
 
+class _DeferredCuda:
+    """A large CUDA tensor result whose bytes leave the device only while
+    its frame is being sent (see _send_buffer)."""
+
+    def __init__(self, lib, ptr, nbytes):
+        self.lib = lib
+        self.ptr = ptr
+        self.nbytes = nbytes
+
+
+def _send_buffer(fd, view):
+    """Write one out-of-band result buffer as a frame on ``fd``."""
+    if not isinstance(view, _DeferredCuda):
+        _write_frame(fd, view)
+        return
+    import ctypes
+
+    rc = view.lib.csp_d2h_stream_fd(
+        fd, ctypes.c_void_p(view.ptr), view.nbytes, STREAM_CHUNK, None, None
+    )
+    if rc != 0:
+        # R1 has already promised this frame, and a frame that failed
+        # part-way cannot be made valid: leave, so the dispatcher sees
+        # ChannelClosed after the ack instead of a shifted stream
+        sys.stderr.write(
+            "csp worker: csp_d2h_stream_fd failed (rc=%d): %s\n"
+            % (rc, view.lib.csp_last_error().decode(errors="replace"))
+        )
+        sys.stderr.flush()
+        os._exit(4)
+
+
 def _stage_result(result, stats, buffers, buffer_meta):
     """Replace large tensors in ``result`` with out-of-band buffer
-    markers; CUDA tensors are staged through hipHostMalloc-pinned memory
-    (fast D2H), large contiguous CPU tensors are shipped zero-copy from
-    their own storage.  Small tensors stay inline in the pickle."""
+    markers.  A large CUDA tensor is only recorded here (device pointer,
+    byte count, the tensor as keep-alive); the send loop streams it
+    through hipHostMalloc-pinned memory.  Large contiguous CPU tensors
+    are shipped zero-copy from their own storage.  Small tensors stay
+    inline in the pickle."""
     if "torch" not in sys.modules:
         return result
     import ctypes
@@ -242,19 +289,12 @@ def _stage_result(result, stats, buffers, buffer_meta):
                     "not available on this GPU host"
                 )
             src_t = t.contiguous()
+            # the library's copy stream does not wait on the null stream
             torch.cuda.synchronize()
-            dst = lib.csp_staging_alloc(nbytes)
-            if not dst:
-                raise RuntimeError("csp_staging_alloc failed")
-            rc = lib.csp_memcpy_d2h(
-                ctypes.c_void_p(dst), ctypes.c_void_p(src_t.data_ptr()), nbytes
-            )
-            if rc != 0:
-                raise RuntimeError("csp_memcpy_d2h failed")
-            view = (ctypes.c_char * nbytes).from_address(dst)
+            view = _DeferredCuda(lib, src_t.data_ptr(), nbytes)
             stats["pinned_tensors"] += 1
             stats["mode"] = "pinned"
-            return emit_buffer(view, None, src_t.dtype, src_t.shape)
+            return emit_buffer(view, src_t, src_t.dtype, src_t.shape)
         # large CPU tensor: zero-copy out-of-band (keep tensor alive)
         src_t = t.contiguous()
         view = (ctypes.c_char * nbytes).from_address(src_t.data_ptr())
@@ -448,7 +488,7 @@ def _serve_isolated(request):
             _write_frame(w, pickle.dumps(("R1", result_blob, meta, len(buffers))))
             wrote_reply = True
             for view, _keep in buffers:
-                _write_frame(w, view)
+                _send_buffer(w, view)
         except BaseException as e:  # noqa: BLE001 - report anything reportable
             # Fallback error reply ONLY if the real R1 never went out: a
             # failure mid-buffer-stream must NOT append a second R1 that
@@ -555,7 +595,7 @@ def main():
         result_blob, meta, buffers = _serve_one(request)
         _write_frame(_proto_fd, pickle.dumps(("R1", result_blob, meta, len(buffers))))
         for view, _keep in buffers:
-            _write_frame(_proto_fd, view)
+            _send_buffer(_proto_fd, view)
         del buffers
         if _gpu_lib is not None:
             _gpu_lib.csp_staging_release_all()

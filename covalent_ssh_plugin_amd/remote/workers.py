@@ -162,9 +162,9 @@ def _reconstruct(result, buffer_meta, buffers):
         info = buffer_meta[i]
         dtype = getattr(torch, info["dtype"])
         raw = buffers[i]
-        # large frames arrive as a preallocated bytearray (zero-copy
+        # large frames arrive in a preallocated writable buffer (zero-copy
         # here); small ones as bytes (copy once into writable memory)
-        data = raw if isinstance(raw, bytearray) else bytearray(raw)
+        data = bytearray(raw) if isinstance(raw, bytes) else raw
         t = torch.frombuffer(data, dtype=dtype)
         return t.reshape(info["shape"])
 

@@ -90,20 +90,12 @@ class LocalTransport(Transport):
         await asyncio.to_thread(shutil.copyfile, src, local_path)
 
     async def open_channel(self, command: str, env: Optional[dict] = None):
-        from .channel import Channel
+        from .channel import spawn_channel_process
 
         full_cmd = self._env_prefix(env) + command
-        proc = await asyncio.create_subprocess_exec(
-            "bash",
-            "-c",
-            full_cmd,
-            cwd=str(self._home),
-            stdin=asyncio.subprocess.PIPE,
-            stdout=asyncio.subprocess.PIPE,
-            stderr=None,
-            limit=64 * 1024 * 1024,
+        return await spawn_channel_process(
+            ["bash", "-c", full_cmd], label="local-worker", cwd=str(self._home)
         )
-        return Channel(proc, label=f"local-worker")
 
     async def open_pipe(self, command: str, env: Optional[dict] = None):
         full_cmd = self._env_prefix(env) + command

@@ -207,17 +207,10 @@ class OpenSSHTransport(Transport):
             raise FileNotFoundError(f"{self.endpoint}:{remote_path}: {err}")
 
     async def open_channel(self, command: str, env: Optional[dict] = None):
-        from .channel import Channel
+        from .channel import spawn_channel_process
 
         argv = self._base_args() + [self.hostname, "--", self._env_prefix(env) + command]
-        proc = await asyncio.create_subprocess_exec(
-            *argv,
-            stdin=asyncio.subprocess.PIPE,
-            stdout=asyncio.subprocess.PIPE,
-            stderr=None,
-            limit=64 * 1024 * 1024,
-        )
-        return Channel(proc, label=f"worker@{self.endpoint}")
+        return await spawn_channel_process(argv, label=f"worker@{self.endpoint}")
 
     async def open_pipe(self, command: str, env: Optional[dict] = None):
         argv = self._base_args() + [self.hostname, "--", self._env_prefix(env) + command]

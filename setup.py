@@ -27,7 +27,7 @@ setup(
     long_description_content_type="text/markdown",
     packages=find_packages(include=["covalent_ssh_plugin_amd*"]),
     package_data={
-        "covalent_ssh_plugin_amd": ["ops/*.so", "ops/hip/*.hip", "remote/stub_template.py"],
+        "covalent_ssh_plugin_amd": ["ops/*.so", "ops/hip/*.hip", "ops/csrc/*.cpp", "ops/csrc/*.h", "remote/stub_template.py"],
     },
     # runtime deps live in requirements.txt (reference setup.py:28-34
     # parses the same file; license CI checks it)
