@@ -7,7 +7,10 @@ gfx950 only) provides:
   and bf16 MFMA throughput from the hand-written warm-up kernels,
 * ``csp_warmup`` — clock/cache warm-up spin (MFMA + HBM sweep),
 * ``csp_staging_get`` / ``csp_host_alloc`` / ``csp_host_free`` /
-  ``csp_memcpy_d2h`` / ``csp_memcpy_h2d`` — hipHostMalloc-pinned staging.
+  ``csp_memcpy_d2h`` / ``csp_memcpy_h2d`` — hipHostMalloc-pinned staging,
+* ``csp_d2h_stream_fd`` / ``csp_h2d_stream_fd`` — one framed tensor buffer
+  between device memory and a channel fd, the copy overlapped with the I/O,
+* ``csp_checksum_dev`` — the argument checksum over bytes in HBM.
 
 On a GPU box these bindings FAIL LOUDLY if the extension is missing or
 broken — there is no eager/CPU fallback for the device path.
@@ -89,6 +92,20 @@ def load(path: str = "") -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_double),
         ctypes.POINTER(ctypes.c_double),
     ]
+    lib.csp_h2d_stream_fd.restype = ctypes.c_int
+    lib.csp_h2d_stream_fd.argtypes = [
+        ctypes.c_int,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_size_t,
+        ctypes.c_int,
+        ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_checksum_dev.restype = ctypes.c_int
+    lib.csp_checksum_dev.argtypes = [
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
+    ]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -169,6 +186,45 @@ def stream_d2h_to_fd(fd: int, data_ptr: int, nbytes: int, chunk_bytes: int = 0) 
         ctypes.byref(d2h_ms), ctypes.byref(write_ms),
     )
     return {"rc": rc, "d2h_ms": d2h_ms.value, "write_ms": write_ms.value}
+
+
+# csp_h2d_stream_fd return codes
+H2D_OK = 0
+H2D_FAILED_DRAINED = 1  # a HIP call failed; the frame was still consumed
+H2D_FAILED_STREAM = 2  # EOF, I/O error, timeout, header mismatch
+
+
+def stream_fd_to_device(
+    fd: int, data_ptr: int, nbytes: int, chunk_bytes: int = 0, timeout_ms: int = -1
+) -> dict:
+    """Read one frame (8-byte big-endian length, which must equal
+    ``nbytes``, then the bytes) from ``fd`` into device memory at
+    ``data_ptr``, the H2D copy overlapped with the reads through the
+    two-chunk pinned ring.  ``data_ptr`` 0 consumes and discards the frame.
+    ``timeout_ms`` bounds each wait for the next byte; negative means no
+    limit.  Returns ``{"rc", "read_ms", "h2d_ms"}``; ``rc`` is one of the
+    H2D_* codes, not an exception: only the caller knows what an unaligned
+    stream means for it."""
+    lib = load()
+    read_ms = ctypes.c_double()
+    h2d_ms = ctypes.c_double()
+    rc = lib.csp_h2d_stream_fd(
+        fd, ctypes.c_void_p(data_ptr), nbytes, chunk_bytes, timeout_ms,
+        ctypes.byref(read_ms), ctypes.byref(h2d_ms),
+    )
+    return {"rc": rc, "read_ms": read_ms.value, "h2d_ms": h2d_ms.value}
+
+
+def checksum_device(data_ptr: int, nbytes: int) -> tuple:
+    """``(s0, s1)`` of ``nbytes`` at the 16-byte aligned device pointer
+    ``data_ptr``: the same two numbers as ``native_io.checksum`` over the
+    same bytes.  Runs on the library's copy stream; data written on another
+    stream must be complete (``torch.cuda.synchronize()``) first."""
+    lib = load()
+    out = (ctypes.c_uint64 * 2)()
+    _check(lib, lib.csp_checksum_dev(ctypes.c_void_p(data_ptr), nbytes, out),
+           "csp_checksum_dev")
+    return int(out[0]), int(out[1])
 
 
 def staged_d2h_bytes(data_ptr: int, nbytes: int) -> bytes:

@@ -74,7 +74,7 @@ def build_io(force: bool = False, verbose: bool = True) -> Path:
     _run(
         [
             host_cxx(),
-            "-O2",
+            "-O3",  # the checksum loop wants the vectoriser (gcc < 12: not at -O2)
             "-std=c++17",
             "-fPIC",
             "-shared",

@@ -9,6 +9,8 @@
 //   csp_io_write_full  the same contract for writes
 //   csp_io_alloc/free  anonymous mapping that asks for transparent huge
 //                      pages, as the destination of a large frame
+//   csp_io_checksum    the two-word argument checksum (definition in
+//                      csp_io.h), computed where the tensor leaves
 //
 // Return codes: see csp_io.h.
 
@@ -40,6 +42,16 @@ void* csp_io_alloc(size_t n) {
 int csp_io_free(void* p, size_t n) {
     if (!p || n == 0) return 0;
     return munmap(p, n) == 0 ? 0 : -errno;
+}
+
+// The loop is inlined here once per clone: the AVX2 one (picked at load time
+// where the CPU has it) does four u32 x u32 -> u64 products per instruction,
+// the baseline SSE2 one two.
+#if defined(__x86_64__) && defined(__GNUC__) && !defined(__clang__)
+__attribute__((target_clones("avx2", "default")))
+#endif
+void csp_io_checksum(const void* src, size_t n, uint64_t out[2]) {
+    csp_io_detail::checksum(src, n, out);
 }
 
 }  // extern "C"

@@ -2,6 +2,9 @@
 // libcsp_gpu.so (csp_gpu.hip, the streaming D2H sender).  Header-only so
 // the GPU library does not have to link the host library; no HIP, no ROCm.
 //
+// Also the host half of the argument checksum (checksum() below); the GPU
+// half is csp_checksum_kernel in csp_gpu.hip and must agree bit for bit.
+//
 // Return codes (the C ABI in csp_io.cpp passes them through):
 //   CSP_IO_OK       all n bytes moved
 //   CSP_IO_EOF      read side only: the peer closed before n bytes arrived
@@ -13,6 +16,8 @@
 #include <cerrno>
 #include <csignal>
 #include <cstddef>
+#include <cstdint>
+#include <cstring>
 #include <ctime>
 
 #include <poll.h>
@@ -123,6 +128,38 @@ static inline int write_full(int fd, const void* src, size_t n, size_t* done) {
     }
     if (done) *done = put;
     return rc;
+}
+
+// Checksum of n payload bytes, identical on host and GPU.  The bytes are
+// taken as little-endian u32 words w_0 .. w_{m-1}, m = ceil(n/4), the last
+// word zero-padded; both sums wrap modulo 2^64:
+//   out[0] = sum w_i
+//   out[1] = sum w_i * ((i mod 2^32) + 1)
+// Integer addition is associative, so any reduction order gives the same
+// two numbers.  Any pointer alignment, any n; n == 0 gives (0, 0).
+//
+// The loop adds w_i * (i mod 2^32), a u32 x u32 -> u64 product that the
+// compiler can vectorise, and the "+ 1" term is out[0] added once at the
+// end.
+static inline void checksum(const void* src, size_t n, uint64_t out[2]) {
+    const unsigned char* p = static_cast<const unsigned char*>(src);
+    const size_t full = n / 4;
+    uint64_t s0 = 0, s1 = 0;
+    uint32_t idx = 0;  // i mod 2^32, kept 32 bits wide so the product stays u32 x u32
+    for (size_t i = 0; i < full; ++i, ++idx) {
+        uint32_t w;
+        memcpy(&w, p + 4 * i, 4);  // unaligned-safe; little-endian hosts only
+        s0 += w;
+        s1 += uint64_t(w) * idx;
+    }
+    if (n & 3) {
+        uint32_t w = 0;
+        memcpy(&w, p + 4 * full, n & 3);
+        s0 += w;
+        s1 += uint64_t(w) * uint32_t(full);
+    }
+    out[0] = s0;
+    out[1] = s1 + s0;
 }
 
 }  // namespace csp_io_detail

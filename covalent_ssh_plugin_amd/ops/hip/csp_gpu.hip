@@ -17,7 +17,13 @@
 //   * csp_d2h_stream_fd
 //                     — a large tensor result framed straight onto the
 //                       worker's channel fd, its D2H copy overlapped with
-//                       the pipe writes through a two-chunk pinned ring.
+//                       the pipe writes through a two-chunk pinned ring,
+//   * csp_h2d_stream_fd
+//                     — the mirror for large tensor arguments: a frame read
+//                       from the channel fd lands in HBM chunk by chunk, the
+//                       H2D copy overlapped with the reads,
+//   * csp_checksum_dev — two-word integer checksum of a device buffer (the
+//                       worker compares it with the dispatcher's).
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -559,6 +565,271 @@ extern "C" int csp_d2h_stream_fd(int fd, const void* src_dev, size_t nbytes,
     if (d2h_ms) *d2h_ms = t_d2h;
     if (write_ms) *write_ms = t_write;
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Streaming H2D: one length-framed buffer from an fd into device memory
+// ---------------------------------------------------------------------------
+//
+// The mirror of csp_d2h_stream_fd for tensor ARGUMENTS.  Reads the 8-byte
+// big-endian frame length (it must equal nbytes), then the payload chunk by
+// chunk into the same two-chunk pinned ring: while chunk i is copied to
+// dst_dev on copy_stream(), chunk i+1 is read from fd into the other slot.
+// A slot is refilled only after the event behind its last copy has fired.
+// Never asks fd for a byte past the frame.
+//
+// A failure on the request side can still be reported as a task error as
+// long as the stream stays aligned, hence three outcomes:
+#define CSP_H2D_OK 0              // frame consumed, data on the device
+                                  // (dst_dev == nullptr: consumed and discarded)
+#define CSP_H2D_FAILED_DRAINED 1  // a HIP call failed; the rest of the frame was
+                                  // read and discarded, the stream is aligned
+#define CSP_H2D_FAILED_STREAM 2   // EOF, I/O error, timeout or header mismatch:
+                                  // the stream is unusable
+//
+// After the first HIP error no further copy is issued; the call only drains.
+// read_ms (optional): host time inside read().  h2d_ms (optional): copy-engine
+// time summed over the chunks, from events around each copy.
+extern "C" int csp_h2d_stream_fd(int fd, void* dst_dev, size_t nbytes,
+                                 size_t chunk_bytes, int timeout_ms,
+                                 double* read_ms, double* h2d_ms) {
+    if (read_ms) *read_ms = 0.0;
+    if (h2d_ms) *h2d_ms = 0.0;
+    double t_read = 0.0, t_h2d = 0.0;
+    int rc = CSP_H2D_OK;
+
+    auto timed_read = [&](void* p, size_t n) -> bool {
+        const double t0 = mono_ms();
+        int io_rc = csp_io_detail::read_full(fd, p, n, timeout_ms, nullptr);
+        t_read += mono_ms() - t0;
+        if (io_rc == CSP_IO_OK) return true;
+        if (io_rc == CSP_IO_EOF)
+            snprintf(g_err, sizeof(g_err), "stream read: end of file inside the frame");
+        else if (io_rc == CSP_IO_TIMEOUT)
+            snprintf(g_err, sizeof(g_err), "stream read: timed out");
+        else
+            snprintf(g_err, sizeof(g_err), "stream read: %s", strerror(-io_rc));
+        rc = CSP_H2D_FAILED_STREAM;
+        return false;
+    };
+
+    unsigned char header[8];
+    if (!timed_read(header, sizeof(header))) {
+        if (read_ms) *read_ms = t_read;
+        return rc;
+    }
+    unsigned long long announced = 0;
+    for (int i = 0; i < 8; ++i) announced = (announced << 8) | header[i];
+    if (announced != (unsigned long long)nbytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "stream header announces %llu bytes, expected %llu", announced,
+                 (unsigned long long)nbytes);
+        if (read_ms) *read_ms = t_read;
+        return CSP_H2D_FAILED_STREAM;
+    }
+
+    if (chunk_bytes == 0) chunk_bytes = kStreamChunkDefault;
+    if (chunk_bytes > nbytes) chunk_bytes = nbytes;  // small payload: one short chunk
+    const size_t nchunks = nbytes ? (nbytes + chunk_bytes - 1) / chunk_bytes : 0;
+    const int ring = nchunks < (size_t)kStreamRing ? (int)nchunks : kStreamRing;
+
+    hipStream_t s = copy_stream();
+    void* buf[kStreamRing] = {nullptr, nullptr};
+    hipEvent_t ev_start[kStreamRing] = {nullptr, nullptr};
+    hipEvent_t ev_done[kStreamRing] = {nullptr, nullptr};
+    bool in_flight[kStreamRing] = {false, false};  // a copy recorded, not yet timed
+    char* dst = static_cast<char*>(dst_dev);
+    bool copies_issued = false;
+    bool hip_failed = false;  // g_err holds the first HIP error
+    size_t consumed = 0;      // payload bytes taken off fd
+
+    auto fail_hip = [&](const char* what, hipError_t e) {
+        if (!hip_failed) set_err(what, e);
+        hip_failed = true;
+    };
+    // wait for the copy that last used `slot`, and add its time
+    auto retire = [&](int slot) {
+        if (!in_flight[slot]) return;
+        in_flight[slot] = false;
+        hipError_t e = hipEventSynchronize(ev_done[slot]);
+        if (e != hipSuccess) { fail_hip("hipEventSynchronize", e); return; }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev_start[slot], ev_done[slot]) == hipSuccess)
+            t_h2d += ms;
+    };
+
+    if (dst) {
+        for (int k = 0; k < ring && !hip_failed; ++k) {
+            buf[k] = csp_staging_alloc(chunk_bytes);
+            if (!buf[k]) { hip_failed = true; break; }  // g_err set
+            hipError_t e = hipEventCreate(&ev_start[k]);
+            if (e == hipSuccess) e = hipEventCreate(&ev_done[k]);
+            if (e != hipSuccess) fail_hip("hipEventCreate", e);
+        }
+    }
+
+    for (size_t i = 0; dst && i < nchunks && !hip_failed; ++i) {
+        const int slot = (int)(i % kStreamRing);
+        const size_t off = i * chunk_bytes;
+        const size_t len = std::min(chunk_bytes, nbytes - off);
+        retire(slot);  // chunk i-2 has left this slot
+        if (hip_failed) break;
+        if (!timed_read(buf[slot], len)) break;
+        consumed += len;
+        hipError_t e = hipEventRecord(ev_start[slot], s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(dst + off, buf[slot], len, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipEventRecord(ev_done[slot], s);
+        copies_issued = true;
+        if (e != hipSuccess) { fail_hip("stream chunk copy", e); break; }
+        in_flight[slot] = true;
+    }
+
+    // Drain mode, or a HIP failure part-way: take the rest of the frame off
+    // fd into plain host memory (the ring may still have copies in flight)
+    // so the next frame starts where the peer put it.
+    if (rc == CSP_H2D_OK && consumed < nbytes) {
+        std::vector<char> scratch(std::min(nbytes - consumed, size_t(1) << 20));
+        while (consumed < nbytes) {
+            const size_t len = std::min(scratch.size(), nbytes - consumed);
+            if (!timed_read(scratch.data(), len)) break;
+            consumed += len;
+        }
+    }
+
+    // No copy may still read a ring buffer once it is back in the pool, and
+    // the caller may use dst_dev on any stream after this returns.
+    if (copies_issued) {
+        hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) fail_hip("hipStreamSynchronize", e);
+    }
+    for (int k = 0; k < kStreamRing; ++k) {
+        if (!hip_failed) retire(k);  // already complete: only adds its time
+        if (ev_start[k]) (void)hipEventDestroy(ev_start[k]);
+        if (ev_done[k]) (void)hipEventDestroy(ev_done[k]);
+        staging_release_one(buf[k]);
+    }
+    if (read_ms) *read_ms = t_read;
+    if (h2d_ms) *h2d_ms = t_h2d;
+    if (rc == CSP_H2D_OK && hip_failed) rc = CSP_H2D_FAILED_DRAINED;
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Argument checksum on the device
+// ---------------------------------------------------------------------------
+//
+// The same two numbers as csp_io_detail::checksum (csp_io.h) over bytes that
+// are already in HBM: little-endian u32 words w_i, s0 = sum w_i,
+// s1 = sum w_i * ((i mod 2^32) + 1), both modulo 2^64.  Integer sums are
+// exact in any order, so the block/grid decomposition cannot change them.
+//
+//   - grid-stride over 16-byte vectors (one global_load_dwordx4 per lane
+//     per trip), 256-thread blocks = 4 waves of 64, at most 1024 blocks
+//     like the HBM sweep; 4 independent loads in flight per lane;
+//   - each lane keeps two u64 accumulators: s0 and t = sum w_i * (i mod
+//     2^32), a u32 x u32 -> u64 multiply-add; s1 = t + s0;
+//   - wave reduction by shuffles, block reduction through LDS, then one
+//     atomicAdd per block and sum on two device u64;
+//   - the n mod 16 tail bytes are read one by one by lane 0 of block 0.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+static const int kChecksumUnroll = 4;
+
+__device__ __forceinline__ void checksum_add(unsigned long long& s0,
+                                             unsigned long long& t,
+                                             u32x4 v, unsigned int word0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s0 += v[j];
+        t += (unsigned long long)v[j] * (unsigned int)(word0 + j);
+    }
+}
+
+__global__ __launch_bounds__(256) void csp_checksum_kernel(
+    const u32x4* __restrict__ src, size_t n16, const unsigned char* __restrict__ tail,
+    unsigned int tail_bytes, unsigned long long* __restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long s0 = 0, t = 0;
+    for (; i + (kChecksumUnroll - 1) * stride < n16; i += kChecksumUnroll * stride) {
+        u32x4 v[kChecksumUnroll];
+#pragma unroll
+        for (int u = 0; u < kChecksumUnroll; ++u) v[u] = src[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < kChecksumUnroll; ++u)
+            checksum_add(s0, t, v[u], (unsigned int)((i + u * stride) * 4));
+    }
+    for (; i < n16; i += stride) checksum_add(s0, t, src[i], (unsigned int)(i * 4));
+
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (unsigned int b = 0; b < tail_bytes; ++b) {
+            const unsigned long long w = (unsigned long long)tail[b] << (8 * (b & 3));
+            s0 += w;
+            t += w * (unsigned int)(n16 * 4 + (b >> 2));
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+static std::mutex g_checksum_mu;
+
+// Checksum of nbytes at device pointer dev (16-byte aligned) into out[2].
+// Runs on copy_stream(), so it is ordered after the copies that
+// csp_h2d_stream_fd issued, and synchronises that stream before returning.
+extern "C" int csp_checksum_dev(const void* dev, size_t nbytes, uint64_t out[2]) {
+    out[0] = out[1] = 0;
+    if (nbytes == 0) return 0;
+    if (reinterpret_cast<uintptr_t>(dev) % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_checksum_dev: device pointer %p is not 16-byte aligned", dev);
+        return -1;
+    }
+    // one accumulator pair per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static int acc_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (acc == nullptr || acc_device != device) {
+        if (acc) (void)hipFree(acc);
+        acc = nullptr;
+        HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+        acc_device = device;
+    }
+    const size_t n16 = nbytes / 16;
+    const unsigned int tail_bytes = (unsigned int)(nbytes % 16);
+    size_t blocks = (n16 + 255) / 256;
+    if (blocks < 1) blocks = 1;  // tail only
+    if (blocks > 1024) blocks = 1024;
+    hipStream_t s = copy_stream();
+    HIP_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(csp_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       static_cast<const u32x4*>(dev), n16,
+                       static_cast<const unsigned char*>(dev) + n16 * 16, tail_bytes,
+                       acc);
+    HIP_TRY(hipGetLastError());
+    unsigned long long host[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out[0] = host[0];
+    out[1] = host[1];
+    return 0;
 }
 
 // On-box variant exploration for the HBM sweep (tools only; the probe

@@ -20,7 +20,14 @@ Protocol (all frames: 8-byte big-endian length + payload):
   request  = pickle dict {"op_id", "workdir", "function_blob",
              "arg_buffers": [{dtype, shape}, ...]} followed by one RAW
              frame per entry (large CPU-tensor arguments, mirrored from
-             the dispatcher without pickle copies)
+             the dispatcher without pickle copies).  An entry marked
+             {"device": true} (executor option device_tensor_args) is not
+             read into host memory at all: csp_h2d_stream_fd takes its
+             frame off stdin chunk by chunk through the pinned ring, each
+             chunk's H2D copy running while the next is read, and the
+             electron gets a CUDA tensor.  When the entry carries
+             "sum": [s0, s1], csp_checksum_dev recomputes the checksum
+             over the bytes in HBM and a mismatch fails the task.
   ack      = pickle tuple ("A1", op_id) — written as soon as the request
              (and its arg frames) has been fully received, BEFORE any
              user code runs.  The dispatcher uses it to distinguish
@@ -165,6 +172,22 @@ def _load_gpu_lib():
         ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_double),
         ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_h2d_stream_fd.restype = ctypes.c_int
+    lib.csp_h2d_stream_fd.argtypes = [
+        ctypes.c_int,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_size_t,
+        ctypes.c_int,
+        ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_checksum_dev.restype = ctypes.c_int
+    lib.csp_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
     ]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
@@ -357,13 +380,200 @@ def _write_frame(fd, payload):
         view = view[written:]
 
 
+# --- tensor arguments that land on the device -------------------------------
+
+_NO_DEVICE_ARGS = (
+    "device tensor arguments (device_tensor_args) need a GPU worker with "
+    "the CDNA4 library: "
+)
+
+
+def _new_arg_stage():
+    return {"mode": "none", "tensors": 0, "bytes": 0, "verified": 0,
+            "read_ms": 0.0, "h2d_ms": 0.0}
+
+
+def _device_arg_lib():
+    """The CDNA4 library for device arguments, loaded on first use the way
+    _stage_result does.  Raises the documented RuntimeError when torch,
+    a GPU or the library is missing."""
+    global _gpu_lib
+    import importlib.util
+
+    if importlib.util.find_spec("torch") is None:
+        raise RuntimeError(_NO_DEVICE_ARGS + "torch is not installed on the worker")
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError(_NO_DEVICE_ARGS + "the worker sees no GPU")
+    if _gpu_lib is None:
+        if not (GPU_LIB and os.path.exists(GPU_LIB)):
+            raise RuntimeError(_NO_DEVICE_ARGS + "the library was not provisioned")
+        try:
+            _gpu_lib = _load_gpu_lib()
+        except Exception as e:  # noqa: BLE001
+            raise RuntimeError(_NO_DEVICE_ARGS + "loading it failed: %r" % (e,))
+    return _gpu_lib
+
+
+def _verify_device_arg(lib, index, tensor, nbytes, info, stage):
+    """Compare the dispatcher's checksum with csp_checksum_dev's over the
+    bytes in HBM (a zero-byte tensor against (0, 0))."""
+    if "sum" not in info:
+        return
+    import ctypes
+
+    out = (ctypes.c_uint64 * 2)()
+    ptr = tensor.data_ptr() if nbytes else 0
+    if lib.csp_checksum_dev(ctypes.c_void_p(ptr), nbytes, out) != 0:
+        raise RuntimeError(
+            "argument buffer %d: csp_checksum_dev failed: %s"
+            % (index, lib.csp_last_error().decode(errors="replace"))
+        )
+    stage["verified"] += 1
+    got = [int(out[0]), int(out[1])]
+    want = [int(info["sum"][0]), int(info["sum"][1])]
+    if got != want:
+        raise RuntimeError(
+            "argument buffer %d failed its integrity check: the dispatcher "
+            "sent checksum %r, the %d bytes on the device give %r"
+            % (index, want, nbytes, got)
+        )
+
+
+def _receive_device_arg(index, info, stage):
+    """Persistent mode: take argument frame ``index`` off stdin straight
+    into a fresh CUDA tensor.  Whatever goes wrong short of a broken
+    stream, the frame is consumed before the error is raised, so the
+    caller can go on to the next frame and report the error in R1."""
+    import ctypes
+
+    try:
+        lib = _device_arg_lib()
+    except RuntimeError:
+        if _read_frame(0) is None:  # drain with the Python reader
+            os._exit(4)
+        raise
+    import torch
+
+    dtype = getattr(torch, info["dtype"])
+    nbytes = torch.empty((), dtype=dtype).element_size()
+    for dim in info["shape"]:
+        nbytes *= int(dim)
+    alloc_error = None
+    tensor = None
+    # the library's copy stream does not wait on the null stream
+    torch.cuda.synchronize()
+    try:
+        tensor = torch.empty(info["shape"], dtype=dtype, device="cuda")
+    except Exception as e:  # noqa: BLE001 - e.g. out of HBM
+        alloc_error = e  # drain mode below: the frame still has to go
+    ptr = tensor.data_ptr() if (tensor is not None and nbytes) else 0
+    read_ms = ctypes.c_double()
+    h2d_ms = ctypes.c_double()
+    rc = lib.csp_h2d_stream_fd(
+        0, ctypes.c_void_p(ptr), nbytes, STREAM_CHUNK, -1,
+        ctypes.byref(read_ms), ctypes.byref(h2d_ms),
+    )
+    stage["read_ms"] += read_ms.value
+    stage["h2d_ms"] += h2d_ms.value
+    if rc == 2:
+        # the request stream is no longer aligned: same policy as a
+        # failed send, leave so the dispatcher sees ChannelClosed
+        sys.stderr.write(
+            "csp worker: csp_h2d_stream_fd lost the stream: %s\n"
+            % lib.csp_last_error().decode(errors="replace")
+        )
+        sys.stderr.flush()
+        os._exit(4)
+    if alloc_error is not None:
+        raise alloc_error
+    if rc != 0:
+        raise RuntimeError(
+            "argument buffer %d: H2D copy failed (rc=%d): %s"
+            % (index, rc, lib.csp_last_error().decode(errors="replace"))
+        )
+    stage["mode"] = "pinned-h2d"
+    stage["tensors"] += 1
+    stage["bytes"] += nbytes
+    _verify_device_arg(lib, index, tensor, nbytes, info, stage)
+    return tensor
+
+
+def _receive_arg_frames(arg_meta):
+    """Read the request's out-of-band argument frames.  Returns
+    (frames, stage, error); frames is None when stdin ended.  A frame is a
+    bytearray (host) or, for a device entry in persistent mode, the CUDA
+    tensor itself.  The first per-argument error is kept and EVERY frame
+    is still consumed, so the stream stays aligned.
+
+    In isolate mode this process is the zygote and must not touch HIP:
+    device entries are read to host memory like the others and the forked
+    child moves them (_device_args_in_child)."""
+    frames = []
+    stage = _new_arg_stage()
+    error = None
+    for index, info in enumerate(arg_meta):
+        if info.get("device") and not ISOLATE:
+            try:
+                frames.append(_receive_device_arg(index, info, stage))
+            except Exception as e:  # noqa: BLE001
+                frames.append(None)
+                if error is None:
+                    error = e
+            continue
+        f = _read_frame(0)
+        if f is None:
+            return None, stage, error
+        frames.append(bytearray(f))
+    return frames, stage, error
+
+
+def _device_args_in_child(frames, meta_list, stage):
+    """Isolate mode, in the forked child after its prologue: move every
+    device-flagged argument buffer (in host memory, read by the zygote) to
+    the GPU and verify it there.  A pinned ring here would only repeat what
+    torch's own pageable copy does (stage through pinned memory, chunk by
+    chunk), and the receive it could overlap with is already over, so this
+    is a plain ``.cuda()``."""
+    flagged = [i for i, info in enumerate(meta_list) if info.get("device")]
+    if not flagged:
+        return
+    lib = _device_arg_lib()
+    import torch
+
+    for i in flagged:
+        info = meta_list[i]
+        dtype = getattr(torch, info["dtype"])
+        t0 = time.monotonic()
+        if len(frames[i]) == 0:
+            tensor = torch.empty(info["shape"], dtype=dtype, device="cuda")
+        else:
+            tensor = (
+                torch.frombuffer(frames[i], dtype=dtype).reshape(info["shape"]).cuda()
+            )
+        # the library's copy stream does not wait on the null stream
+        torch.cuda.synchronize()
+        stage["h2d_ms"] += (time.monotonic() - t0) * 1000
+        nbytes = tensor.numel() * tensor.element_size()
+        stage["mode"] = "isolated-copy"
+        stage["tensors"] += 1
+        stage["bytes"] += nbytes
+        _verify_device_arg(lib, i, tensor, nbytes, info, stage)
+        frames[i] = tensor
+
+
 def _rebuild_arg_tensors(obj, buffers, meta_list):
     """Mirror of the dispatcher-side marker walk for request buffers."""
     import torch
 
     def build(i):
+        if isinstance(buffers[i], torch.Tensor):
+            return buffers[i]  # a device argument, already in HBM
         info = meta_list[i]
         dtype = getattr(torch, info["dtype"])
+        if len(buffers[i]) == 0:
+            return torch.empty(info["shape"], dtype=dtype)
         return torch.frombuffer(buffers[i], dtype=dtype).reshape(info["shape"])
 
     def walk(o):
@@ -392,18 +602,28 @@ def _serve_one(request):
             "gpu_slot": GPU_SLOT, "buffers": [],
             "hip_visible_devices": os.environ.get("HIP_VISIBLE_DEVICES"),
             "pid": os.getpid(), "worker": True, "served": _served}
+    arg_stage = request.get("_arg_staging") or _new_arg_stage()
+    meta["arg_staging"] = arg_stage
     result = None
     exception = None
     buffers = []
     try:
+        if request.get("_arg_error") is not None:
+            # an argument frame was consumed but could not be delivered:
+            # the electron fails with that error, user code does not run
+            raise request["_arg_error"]
         fn, args, kwargs = pickle.loads(request["function_blob"])
         arg_bufs = request.get("_arg_buffer_frames") or []
         if arg_bufs:
+            if ISOLATE:
+                _device_args_in_child(arg_bufs, request["arg_buffers"], arg_stage)
             args = _rebuild_arg_tensors(args, arg_bufs, request["arg_buffers"])
             kwargs = _rebuild_arg_tensors(kwargs, arg_bufs, request["arg_buffers"])
     except Exception as e:  # noqa: BLE001
         exception = e
         fn = None
+    for key in ("read_ms", "h2d_ms"):
+        arg_stage[key] = round(arg_stage[key], 3)
 
     home = os.getcwd()
     if exception is None:
@@ -577,15 +797,14 @@ def main():
         if frame is None or frame == b"":
             break
         request = pickle.loads(frame)
-        n_arg_bufs = len(request.get("arg_buffers") or [])
-        if n_arg_bufs:
-            frames = []
-            for _ in range(n_arg_bufs):
-                f = _read_frame(0)
-                if f is None:
-                    return
-                frames.append(bytearray(f))
+        arg_meta = request.get("arg_buffers") or []
+        if arg_meta:
+            frames, arg_stage, arg_error = _receive_arg_frames(arg_meta)
+            if frames is None:
+                return
             request["_arg_buffer_frames"] = frames
+            request["_arg_staging"] = arg_stage
+            request["_arg_error"] = arg_error
         # ack AFTER the full request is in hand, BEFORE user code runs:
         # the dispatcher's retry-on-death policy keys off this frame
         _write_frame(_proto_fd, pickle.dumps(("A1", request.get("op_id"))))
@@ -597,6 +816,7 @@ def main():
         for view, _keep in buffers:
             _send_buffer(_proto_fd, view)
         del buffers
+        request = None  # lets go of device arguments before the next wait
         if _gpu_lib is not None:
             _gpu_lib.csp_staging_release_all()
 

@@ -20,6 +20,7 @@ from typing import Dict, Optional, Tuple
 import cloudpickle
 
 from ..compat import app_log
+from ..transport import native_io
 from ..transport.channel import Channel, ChannelClosed
 
 WorkerKey = Tuple[object, ...]
@@ -103,12 +104,20 @@ async def get_worker(key: WorkerKey, launcher, startup_timeout: float = 180.0) -
         return handle
 
 
-def extract_arg_buffers(args, kwargs, threshold: int):
+def extract_arg_buffers(args, kwargs, threshold: int, to_device: bool = False):
     """Pull large contiguous CPU torch tensors out of (args, kwargs) and
     replace them with out-of-band buffer markers (the request-direction
     mirror of the worker's result staging).  Returns
     (new_args, new_kwargs, buffer_meta, buffers); no-op (and no torch
-    import) unless torch is already loaded in the dispatcher."""
+    import) unless torch is already loaded in the dispatcher.
+
+    ``to_device`` (the executor's ``device_tensor_args``): EVERY CPU tensor
+    is extracted whatever its size, so an electron never gets a mix of CPU
+    and CUDA tensors that depends on a threshold.  Each meta entry is
+    marked ``"device": True`` (the worker lands it in HBM) and, when the
+    native I/O library is loaded, carries ``"sum": [s0, s1]``, the checksum
+    of the contiguous bytes that will be sent (the worker recomputes it on
+    the GPU and compares)."""
     import sys
 
     if "torch" not in sys.modules:
@@ -125,16 +134,20 @@ def extract_arg_buffers(args, kwargs, threshold: int):
         nbytes = src_t.numel() * src_t.element_size()
         view = (ctypes.c_char * nbytes).from_address(src_t.data_ptr())
         buffers.append((view, src_t))  # keep tensor alive until sent
-        buffer_meta.append(
-            {"dtype": str(src_t.dtype).replace("torch.", ""), "shape": list(src_t.shape)}
-        )
+        info = {"dtype": str(src_t.dtype).replace("torch.", ""), "shape": list(src_t.shape)}
+        if to_device:
+            info["device"] = True
+            # looked up at call time: None when libcsp_io.so is not loaded
+            sums = native_io.checksum(view)
+            if sums is not None:
+                info["sum"] = [int(sums[0]), int(sums[1])]
+        buffer_meta.append(info)
         return ("__csp_tensor_buffer_v1__", len(buffers) - 1)
 
     def walk(obj):
         if isinstance(obj, torch.Tensor):
-            if (
-                not obj.is_cuda
-                and obj.numel() * obj.element_size() >= threshold
+            if not obj.is_cuda and (
+                to_device or obj.numel() * obj.element_size() >= threshold
             ):
                 return extract(obj)
             return obj

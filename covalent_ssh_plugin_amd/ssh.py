@@ -100,6 +100,14 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # each fork copies the torch-ROCm address space, ~250 ms on MI355X)
     # or "none" (millisecond forks; torch electrons import themselves).
     "isolate_preload": "torch",
+    # CPU torch tensors in an electron's args/kwargs arrive in the electron
+    # as CUDA tensors on the worker's GPU: received straight into HBM
+    # through a pinned ring (the copy overlaps the receive) and verified
+    # there against a checksum computed here.  Needs persistent_workers or
+    # isolate_tasks (the fused and stub paths keep arguments inside the
+    # pickle file).  The run_local_on_ssh_fail fallback runs the function
+    # with the original CPU tensors.
+    "device_tensor_args": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -290,6 +298,7 @@ class SSHExecutor(RemoteExecutor):
         persistent_workers: Optional[bool] = None,
         isolate_tasks: Optional[bool] = None,
         isolate_preload: str = "",
+        device_tensor_args: Optional[bool] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -341,6 +350,14 @@ class SSHExecutor(RemoteExecutor):
         self.persistent_workers = bool(
             _conf("persistent_workers", persistent_workers, default=False)
         ) or self.isolate_tasks  # isolation rides the worker channel
+        self.device_tensor_args = bool(
+            _conf("device_tensor_args", device_tensor_args, default=False)
+        )
+        if self.device_tensor_args and not self.persistent_workers:
+            raise ValueError(
+                "device_tensor_args needs persistent_workers or isolate_tasks: "
+                "only the worker channel carries tensor arguments out of band"
+            )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -1190,7 +1207,8 @@ class SSHExecutor(RemoteExecutor):
                     # inside the pickle (mirror of the result staging)
                     s_args, s_kwargs, arg_meta, arg_bufs = (
                         worker_pool.extract_arg_buffers(
-                            args, kwargs, self.pinned_staging_threshold_bytes
+                            args, kwargs, self.pinned_staging_threshold_bytes,
+                            to_device=self.device_tensor_args,
                         )
                     )
                     function_blob = cloudpickle.dumps((function, s_args, s_kwargs))

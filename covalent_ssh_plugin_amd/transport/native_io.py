@@ -64,6 +64,10 @@ def load(path: str = "") -> Optional[ctypes.CDLL]:
     lib.csp_io_alloc.argtypes = [ctypes.c_size_t]
     lib.csp_io_free.restype = ctypes.c_int
     lib.csp_io_free.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    lib.csp_io_checksum.restype = None
+    lib.csp_io_checksum.argtypes = [
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
+    ]
     _lib = lib
     return lib
 
@@ -111,6 +115,35 @@ def write_full(fd: int, buf, nbytes: Optional[int] = None, offset: int = 0) -> i
         return lib.csp_io_write_full(fd, bytes(window), nbytes)
     carrier = (ctypes.c_char * nbytes).from_buffer(window)
     return lib.csp_io_write_full(fd, ctypes.addressof(carrier), nbytes)
+
+
+def checksum(buf, nbytes: Optional[int] = None, offset: int = 0):
+    """The two-word checksum ``(s0, s1)`` of ``nbytes`` of ``buf[offset:]``
+    (definition in ops/csrc/csp_io.h; the worker's GPU kernel computes the
+    same two numbers over the bytes once they are in HBM).  ``None`` when
+    the library is not loaded: the caller then sends no checksum and the
+    worker verifies nothing.  There is no pure-Python fallback on purpose,
+    it would cost more than the transfer."""
+    lib = load()
+    if lib is None:
+        return None
+    view = memoryview(buf).cast("B")
+    if nbytes is None:
+        nbytes = view.nbytes - offset
+    if offset < 0 or nbytes < 0 or offset + nbytes > view.nbytes:
+        raise ValueError("range outside the buffer")
+    out = (ctypes.c_uint64 * 2)()
+    if nbytes == 0:
+        lib.csp_io_checksum(None, 0, out)
+        return int(out[0]), int(out[1])
+    window = view[offset : offset + nbytes]
+    if window.readonly:
+        # ctypes cannot borrow a read-only buffer; bytes pass by pointer
+        lib.csp_io_checksum(bytes(window), nbytes, out)
+    else:
+        carrier = (ctypes.c_char * nbytes).from_buffer(window)
+        lib.csp_io_checksum(ctypes.addressof(carrier), nbytes, out)
+    return int(out[0]), int(out[1])
 
 
 def alloc_buffer(nbytes: int):
