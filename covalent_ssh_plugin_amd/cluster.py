@@ -55,6 +55,11 @@ class SSHClusterExecutor:
     retries on the next-least-loaded node.  Failures after execution may
     have begun are never failed over (a non-idempotent task could run
     twice); they surface to the caller.
+
+    Every other keyword argument goes to each node's :class:`SSHExecutor`
+    unchanged (``persistent_workers``, ``device_tensor_args``,
+    ``pack_tensor_results``, ``pack_results_min_bytes``, ...), so the
+    executor's own validation applies per node.
     """
 
     def __init__(

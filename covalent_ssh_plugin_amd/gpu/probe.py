@@ -10,7 +10,9 @@ gfx950 only) provides:
   ``csp_memcpy_d2h`` / ``csp_memcpy_h2d`` — hipHostMalloc-pinned staging,
 * ``csp_d2h_stream_fd`` / ``csp_h2d_stream_fd`` — one framed tensor buffer
   between device memory and a channel fd, the copy overlapped with the I/O,
-* ``csp_checksum_dev`` — the argument checksum over bytes in HBM.
+* ``csp_checksum_dev`` — the argument checksum over bytes in HBM,
+* ``csp_pack_dev`` — many small device buffers gathered into one contiguous
+  zero-padded arena by one kernel launch (``pack_tensor_results``).
 
 On a GPU box these bindings FAIL LOUDLY if the extension is missing or
 broken — there is no eager/CPU fallback for the device path.
@@ -106,6 +108,18 @@ def load(path: str = "") -> ctypes.CDLL:
     lib.csp_checksum_dev.argtypes = [
         ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
     ]
+    lib.csp_pack_dev.restype = ctypes.c_int
+    lib.csp_pack_dev.argtypes = [
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_pack_tile_bytes.restype = ctypes.c_size_t
+    lib.csp_pack_tile_bytes.argtypes = []
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -225,6 +239,50 @@ def checksum_device(data_ptr: int, nbytes: int) -> tuple:
     _check(lib, lib.csp_checksum_dev(ctypes.c_void_p(data_ptr), nbytes, out),
            "csp_checksum_dev")
     return int(out[0]), int(out[1])
+
+
+PACK_ALIGN = 16  # every packed segment starts on a multiple of this
+
+
+def pack_layout(sizes) -> tuple:
+    """``(offsets, arena_bytes)`` for segments of ``sizes`` bytes under the
+    layout rule of ``csp_pack_dev``: the first at 0, each next one after the
+    previous size rounded up to 16."""
+    offsets = []
+    total = 0
+    for n in sizes:
+        offsets.append(total)
+        total += (int(n) + PACK_ALIGN - 1) // PACK_ALIGN * PACK_ALIGN
+    return offsets, total
+
+
+def pack_tile_bytes() -> int:
+    """Bytes of one segment that one block moves per trip of the pack kernel."""
+    return int(load().csp_pack_tile_bytes())
+
+
+def pack_device(segments, arena_ptr: int, arena_bytes: int) -> dict:
+    """Gather ``segments``, a sequence of ``(src_ptr, dst_off, nbytes)`` with
+    device pointers, into the 16-byte aligned device arena at ``arena_ptr``
+    with one kernel launch.  The offsets must follow :func:`pack_layout` and
+    ``arena_bytes`` must be its total; a violation raises ``GpuLibError`` and
+    launches nothing.  Afterwards every arena byte outside a segment is zero.
+    Runs on the library's copy stream; sources written on another stream must
+    be complete (``torch.cuda.synchronize()``) first.  Returns
+    ``{"kernel_ms": ...}``, the kernel alone."""
+    lib = load()
+    n = len(segments)
+    src = (ctypes.c_void_p * n)(*[int(s[0]) or None for s in segments])
+    off = (ctypes.c_uint64 * n)(*[int(s[1]) for s in segments])
+    size = (ctypes.c_uint64 * n)(*[int(s[2]) for s in segments])
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_pack_dev(src, off, size, n, ctypes.c_void_p(arena_ptr), arena_bytes,
+                         ctypes.byref(kernel_ms)),
+        "csp_pack_dev",
+    )
+    return {"kernel_ms": kernel_ms.value}
 
 
 def staged_d2h_bytes(data_ptr: int, nbytes: int) -> bytes:

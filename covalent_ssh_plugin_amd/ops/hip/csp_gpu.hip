@@ -23,7 +23,10 @@
 //                       from the channel fd lands in HBM chunk by chunk, the
 //                       H2D copy overlapped with the reads,
 //   * csp_checksum_dev — two-word integer checksum of a device buffer (the
-//                       worker compares it with the dispatcher's).
+//                       worker compares it with the dispatcher's),
+//   * csp_pack_dev    — one launch gathers many small device buffers into a
+//                       contiguous zero-padded arena, so a result of hundreds
+//                       of small tensors leaves as one streamed frame.
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -830,6 +833,267 @@ extern "C" int csp_checksum_dev(const void* dev, size_t nbytes, uint64_t out[2])
     out[0] = host[0];
     out[1] = host[1];
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Result packing: many small device buffers into one contiguous arena
+// ---------------------------------------------------------------------------
+//
+// A result made of hundreds of small CUDA tensors leaves as ONE streamed,
+// checksummed frame: this kernel gathers them into an arena that
+// csp_checksum_dev and csp_d2h_stream_fd then treat as one buffer.
+//
+// Layout (computed by the caller, checked here before anything is launched):
+// segment k is nbytes[k] bytes at src[k] and goes to arena + dst_off[k];
+// dst_off[0] == 0, dst_off[k+1] == dst_off[k] + round_up(nbytes[k], 16),
+// arena_bytes is the sum of the rounded sizes, arena is 16-byte aligned.
+// Every arena byte therefore belongs to the 16-byte vectors of exactly one
+// segment, and the kernel stores each of those vectors once: the 0..15
+// bytes after a segment's data are written as zeros in its last vector.
+//
+//   - one launch for all segments (multi-tensor style): work is cut into
+//     tiles of kPackTileBytes of one segment (256 lanes x 16 B x 4 unrolled
+//     trips, the checksum kernel's unroll); the host builds the prefix of
+//     tile counts, each block loops over tiles and finds its segment by a
+//     binary search that depends on the tile index only (wave-uniform);
+//   - 256-thread blocks, grid = min(total tiles, 2048);
+//   - a 16-byte aligned source moves with nontemporal 16-byte loads, any
+//     other at its own natural alignment (8, 4, 2 or 1 bytes); the stores
+//     are always aligned nontemporal 16-byte stores (nothing is re-read);
+//   - no byte before src[k] or at or after src[k] + nbytes[k] is read: only
+//     vectors wholly inside the segment are loaded whole, the nbytes % 16
+//     tail is read byte by byte and merged with zeros.
+struct PackSeg {
+    const unsigned char* src;
+    unsigned long long dst_off;
+    unsigned long long nbytes;
+    unsigned long long tile_begin;  // tiles owned by the segments before this one
+};
+
+static const int kPackUnroll = 4;
+static const size_t kPackTileVecs = size_t(256) * kPackUnroll;
+static const size_t kPackTileBytes = kPackTileVecs * 16;
+static const size_t kPackGridCap = 2048;
+
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned char u8x16 __attribute__((ext_vector_type(16)));
+
+// Sources come out of a table in memory, so the compiler cannot see that
+// they are global pointers and would use flat loads: say so.
+#define CSP_GLOBAL __attribute__((address_space(1)))
+typedef const CSP_GLOBAL unsigned char* pack_src_t;
+
+// 16 bytes at p, which is ALIGN-byte aligned and has 16 readable bytes.
+// The source states no more alignment than the pointer has; where the
+// compiler fuses the narrow loads into one wider load of the same 16 bytes
+// it does so under the target's unaligned-access mode for global memory.
+template <int ALIGN>
+__device__ __forceinline__ u32x4 pack_load16(pack_src_t p) {
+    if constexpr (ALIGN == 16) {
+        return __builtin_nontemporal_load(reinterpret_cast<const CSP_GLOBAL u32x4*>(p));
+    } else if constexpr (ALIGN == 8) {
+        const CSP_GLOBAL unsigned long long* q =
+            reinterpret_cast<const CSP_GLOBAL unsigned long long*>(p);
+        u64x2 v = {q[0], q[1]};
+        return __builtin_bit_cast(u32x4, v);
+    } else if constexpr (ALIGN == 4) {
+        const CSP_GLOBAL unsigned int* q = reinterpret_cast<const CSP_GLOBAL unsigned int*>(p);
+        u32x4 v = {q[0], q[1], q[2], q[3]};
+        return v;
+    } else if constexpr (ALIGN == 2) {
+        const CSP_GLOBAL unsigned short* q =
+            reinterpret_cast<const CSP_GLOBAL unsigned short*>(p);
+        u16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = q[j];
+        return __builtin_bit_cast(u32x4, v);
+    } else {
+        u8x16 v;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = p[j];
+        return __builtin_bit_cast(u32x4, v);
+    }
+}
+
+// the last `r` (1..15) bytes of a segment, zero-extended to 16
+__device__ __forceinline__ u32x4 pack_load_tail(pack_src_t p, unsigned int r) {
+    unsigned int w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (unsigned int b = 0; b < 15; ++b)
+        if (b < r) w[b >> 2] |= (unsigned int)p[b] << (8 * (b & 3));
+    u32x4 v = {w[0], w[1], w[2], w[3]};
+    return v;
+}
+
+template <int ALIGN>
+__device__ __forceinline__ void pack_tile(pack_src_t src, u32x4* __restrict__ dst,
+                                          size_t nbytes, size_t tile_in_seg) {
+    const size_t nfull = nbytes / 16;  // vectors wholly inside the segment
+    const size_t v0 = tile_in_seg * kPackTileVecs + threadIdx.x;
+    if ((tile_in_seg + 1) * kPackTileVecs <= nfull) {
+        // interior tile: every lane has four whole vectors
+        u32x4 v[kPackUnroll];
+#pragma unroll
+        for (int u = 0; u < kPackUnroll; ++u)
+            v[u] = pack_load16<ALIGN>(src + (v0 + u * 256) * 16);
+#pragma unroll
+        for (int u = 0; u < kPackUnroll; ++u)
+            __builtin_nontemporal_store(v[u], &dst[v0 + u * 256]);
+        return;
+    }
+    const unsigned int tail = (unsigned int)(nbytes % 16);
+#pragma unroll
+    for (int u = 0; u < kPackUnroll; ++u) {
+        const size_t vi = v0 + u * 256;
+        if (vi < nfull)
+            __builtin_nontemporal_store(pack_load16<ALIGN>(src + vi * 16), &dst[vi]);
+        else if (vi == nfull && tail != 0)
+            __builtin_nontemporal_store(pack_load_tail(src + vi * 16, tail), &dst[vi]);
+    }
+}
+
+__global__ __launch_bounds__(256) void csp_pack_kernel(
+    const PackSeg* __restrict__ segs, unsigned int nseg, size_t total_tiles,
+    unsigned char* __restrict__ arena) {
+    for (size_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+        // last segment whose first tile is <= tile (tile_begin is strictly
+        // increasing: the host leaves zero-byte segments out of the table)
+        unsigned int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].tile_begin <= tile) lo = mid; else hi = mid;
+        }
+        const PackSeg s = segs[lo];
+        u32x4* dst = reinterpret_cast<u32x4*>(arena + s.dst_off);
+        const size_t t = tile - s.tile_begin;
+        const pack_src_t src = (pack_src_t)s.src;
+        const unsigned int a = (unsigned int)(reinterpret_cast<uintptr_t>(s.src) & 15u);
+        if (a == 0) pack_tile<16>(src, dst, s.nbytes, t);
+        else if ((a & 7u) == 0) pack_tile<8>(src, dst, s.nbytes, t);
+        else if ((a & 3u) == 0) pack_tile<4>(src, dst, s.nbytes, t);
+        else if ((a & 1u) == 0) pack_tile<2>(src, dst, s.nbytes, t);
+        else pack_tile<1>(src, dst, s.nbytes, t);
+    }
+}
+
+extern "C" size_t csp_pack_tile_bytes() { return kPackTileBytes; }
+
+static std::mutex g_pack_mu;
+
+// Gather nseg device segments into `arena` (layout rule above).  A layout
+// violation returns -1 with a message and launches nothing.  Runs on
+// copy_stream(), so it is ordered before a csp_checksum_dev or
+// csp_d2h_stream_fd of the arena, and synchronises that stream before
+// returning; sources written on another stream must be complete first.
+// kernel_ms (optional): the kernel alone, from events around the launch.
+extern "C" int csp_pack_dev(const void* const* src, const uint64_t* dst_off,
+                            const uint64_t* nbytes, size_t nseg, void* arena,
+                            size_t arena_bytes, double* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (reinterpret_cast<uintptr_t>(arena) % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_pack_dev: arena pointer %p is not 16-byte aligned", arena);
+        return -1;
+    }
+    if (nseg >= (size_t(1) << 31)) {
+        snprintf(g_err, sizeof(g_err), "csp_pack_dev: %zu segments are too many", nseg);
+        return -1;
+    }
+    std::vector<PackSeg> table;
+    table.reserve(nseg);
+    uint64_t expect = 0, tiles = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        if (dst_off[k] != expect) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_pack_dev: dst_off[%zu] is %llu, the layout rule gives %llu", k,
+                     (unsigned long long)dst_off[k], (unsigned long long)expect);
+            return -1;
+        }
+        const uint64_t rounded = (nbytes[k] + 15) & ~uint64_t(15);
+        if (rounded < nbytes[k] || expect + rounded < expect) {
+            snprintf(g_err, sizeof(g_err), "csp_pack_dev: segment %zu overflows", k);
+            return -1;
+        }
+        expect += rounded;
+        if (nbytes[k] == 0) continue;  // owns no tile
+        if (src[k] == nullptr) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_pack_dev: segment %zu has %llu bytes at a null pointer", k,
+                     (unsigned long long)nbytes[k]);
+            return -1;
+        }
+        table.push_back({static_cast<const unsigned char*>(src[k]), dst_off[k],
+                         nbytes[k], tiles});
+        tiles += (rounded + kPackTileBytes - 1) / kPackTileBytes;
+    }
+    if (expect != (uint64_t)arena_bytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_pack_dev: arena_bytes is %zu, the segments need %llu", arena_bytes,
+                 (unsigned long long)expect);
+        return -1;
+    }
+    if (table.empty()) return 0;
+    if (arena == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_pack_dev: null arena for %zu bytes", arena_bytes);
+        return -1;
+    }
+
+    // one grow-only table per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_pack_mu);
+    static PackSeg* dev_table = nullptr;
+    static size_t dev_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_table == nullptr || dev_device != device || dev_cap < table.size()) {
+        if (dev_table) (void)hipFree(dev_table);
+        dev_table = nullptr;
+        dev_cap = 0;
+        size_t cap = 1024;
+        while (cap < table.size()) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_table, cap * sizeof(PackSeg)));
+        dev_cap = cap;
+        dev_device = device;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define PACK_TRY(expr)                                             \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    // `table` outlives the copy: the stream is synchronised below
+    PACK_TRY(hipMemcpyAsync(dev_table, table.data(), table.size() * sizeof(PackSeg),
+                            hipMemcpyHostToDevice, s));
+    const size_t blocks = tiles < kPackGridCap ? (size_t)tiles : kPackGridCap;
+    if (t0) PACK_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_pack_kernel, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       dev_table, (unsigned int)table.size(), (size_t)tiles,
+                       static_cast<unsigned char*>(arena));
+    PACK_TRY(hipGetLastError());
+    if (t1) PACK_TRY(hipEventRecord(t1, s));
+    PACK_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        PACK_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef PACK_TRY
+    return done(0);
 }
 
 // On-box variant exploration for the HBM sweep (tools only; the probe

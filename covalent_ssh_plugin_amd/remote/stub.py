@@ -68,12 +68,16 @@ def render_worker(
     isolate: bool = False,
     isolate_preload: str = "torch",
     telemetry_every: int = 0,
+    pack_results: bool = False,
+    pack_min_bytes: int = 0,
 ) -> str:
     """Return the persistent worker script text (one per endpoint; the
     GPU slot arrives via the CSP_GPU_SLOT env var at launch).  With
     ``isolate`` the worker is a fork-server zygote: every electron runs
     in a freshly forked child process; ``isolate_preload`` picks what
-    the zygote imports pre-fork ("torch" or "none")."""
+    the zygote imports pre-fork ("torch" or "none").  ``pack_results``
+    makes the worker send the small CUDA tensors of a result as one packed
+    frame when they total at least ``pack_min_bytes``."""
     text = _template_text(str(_WORKER_TEMPLATE_PATH))
     thr = DEFAULT_STAGING_THRESHOLD if staging_threshold is None else int(staging_threshold)
     replacements = {
@@ -85,6 +89,8 @@ def render_worker(
         "__CSP_ISOLATE__": repr(bool(isolate)),
         "__CSP_ISOLATE_PRELOAD__": str(isolate_preload),
         "__CSP_TELEMETRY_EVERY__": str(int(telemetry_every)),
+        "__CSP_PACK_RESULTS__": repr(bool(pack_results)),
+        "__CSP_PACK_MIN_BYTES__": str(int(pack_min_bytes)),
     }
     for token, value in replacements.items():
         text = text.replace(token, value)

@@ -44,7 +44,16 @@ Protocol (all frames: 8-byte big-endian length + payload):
              frame is being written), large CPU tensors zero-copy from
              their own storage — skipping both pickle copies on the
              payload.  meta["buffers"][i] carries
-             dtype/shape.  A zero-length request frame means: shut down.
+             dtype/shape.  With the executor option pack_tensor_results the
+             CUDA tensors BELOW the staging threshold do not stay in the
+             pickle either: csp_pack_dev gathers them into one device arena
+             (each at a multiple of 16 bytes, zero padded), the arena goes
+             out as one more streamed frame, each tensor becomes
+             ("__csp_packed_tensor_v1__", i, j), and meta["buffers"][i] is
+             {"packed": [{dtype, shape, offset, nbytes}, ...], "nbytes",
+             "sum": [s0, s1]} with csp_checksum_dev's checksum of the arena,
+             which the dispatcher verifies.  A zero-length request frame
+             means: shut down.
 
 The worker's REAL stdout is reserved for the protocol; fd 1 is
 re-pointed at stderr before any user code runs, so user prints cannot
@@ -64,6 +73,11 @@ STAGING_THRESHOLD = int(__CSP_STAGING_THRESHOLD__)
 # bytes per pinned ring chunk when a CUDA result is streamed to the channel
 STREAM_CHUNK = int(__CSP_STREAM_CHUNK__)
 IDLE_TIMEOUT = float(__CSP_IDLE_TIMEOUT__)  # seconds; 0 = never exit
+# Pack the CUDA tensors of a result that are below STAGING_THRESHOLD into
+# one device arena sent as a single streamed, checksummed frame, when they
+# total at least PACK_MIN_BYTES.
+PACK_RESULTS = bool(__CSP_PACK_RESULTS__)
+PACK_MIN_BYTES = int(__CSP_PACK_MIN_BYTES__)
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
 # break the children) and every electron executes in a freshly forked
@@ -189,6 +203,16 @@ def _load_gpu_lib():
         ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_uint64),
     ]
+    lib.csp_pack_dev.restype = ctypes.c_int
+    lib.csp_pack_dev.argtypes = [
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_double),
+    ]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -241,8 +265,9 @@ def _prologue():
 
 
 class _DeferredCuda:
-    """A large CUDA tensor result whose bytes leave the device only while
-    its frame is being sent (see _send_buffer)."""
+    """A CUDA result buffer (one large tensor, or the arena of packed small
+    ones) whose bytes leave the device only while its frame is being sent
+    (see _send_buffer)."""
 
     def __init__(self, lib, ptr, nbytes):
         self.lib = lib
@@ -272,13 +297,108 @@ def _send_buffer(fd, view):
         os._exit(4)
 
 
+def _small_cuda_tensors(result):
+    """The CUDA tensors of ``result`` below STAGING_THRESHOLD, each object
+    once, in walk order."""
+    import torch
+
+    found = {}
+
+    def walk(obj):
+        if isinstance(obj, torch.Tensor):
+            if obj.is_cuda and obj.numel() * obj.element_size() < STAGING_THRESHOLD:
+                found.setdefault(id(obj), obj)
+        elif isinstance(obj, dict):
+            for v in obj.values():
+                walk(v)
+        elif isinstance(obj, (tuple, list)):
+            for v in obj:
+                walk(v)
+
+    walk(result)
+    return list(found.values())
+
+
+def _pack_small_cuda(lib, result, stats, buffers, buffer_meta):
+    """Gather the small CUDA tensors of ``result`` into one device arena
+    with csp_pack_dev and emit it as one streamed buffer.  Returns
+    {id(tensor): marker}; empty when there is nothing to pack, the total is
+    below PACK_MIN_BYTES, or anything went wrong (the reason then goes to
+    stats["pack_fallback"] and the tensors take the per-tensor path).
+
+    The arena is a transient second copy of the packed tensors in HBM until
+    its frame is sent; only the out-of-memory fallback bounds its size."""
+    import ctypes
+
+    import torch
+
+    tensors = _small_cuda_tensors(result)
+    sizes = [t.numel() * t.element_size() for t in tensors]
+    if not tensors or sum(sizes) == 0 or sum(sizes) < PACK_MIN_BYTES:
+        return {}
+    try:
+        # torch makes non-contiguous tensors contiguous, as on the large path
+        srcs = [t.contiguous() for t in tensors]
+        offsets = []
+        total = 0
+        for n in sizes:
+            offsets.append(total)
+            total += (n + 15) // 16 * 16
+        # the library's copy stream does not wait on the null stream
+        torch.cuda.synchronize()
+        arena = torch.empty(total, dtype=torch.uint8, device="cuda")
+        count = len(srcs)
+        src_ptrs = (ctypes.c_void_p * count)(
+            *[(t.data_ptr() or None) if n else None for t, n in zip(srcs, sizes)]
+        )
+        rc = lib.csp_pack_dev(
+            src_ptrs, (ctypes.c_uint64 * count)(*offsets),
+            (ctypes.c_uint64 * count)(*sizes), count,
+            ctypes.c_void_p(arena.data_ptr()), total, None,
+        )
+        if rc != 0:
+            raise RuntimeError(
+                "csp_pack_dev failed (rc=%d): %s"
+                % (rc, lib.csp_last_error().decode(errors="replace"))
+            )
+        sums = (ctypes.c_uint64 * 2)()
+        rc = lib.csp_checksum_dev(ctypes.c_void_p(arena.data_ptr()), total, sums)
+        if rc != 0:
+            raise RuntimeError(
+                "csp_checksum_dev failed (rc=%d): %s"
+                % (rc, lib.csp_last_error().decode(errors="replace"))
+            )
+    except Exception as e:  # noqa: BLE001 - packing never fails a task
+        stats["pack_fallback"] = repr(e)[:500]
+        return {}
+    del srcs  # their bytes are in the arena
+    buffers.append((_DeferredCuda(lib, arena.data_ptr(), total), arena))
+    buffer_meta.append({
+        "packed": [
+            {"dtype": str(t.dtype).replace("torch.", ""), "shape": list(t.shape),
+             "offset": off, "nbytes": n}
+            for t, off, n in zip(tensors, offsets, sizes)
+        ],
+        "nbytes": total,
+        "sum": [int(sums[0]), int(sums[1])],
+    })
+    index = len(buffers) - 1
+    stats["packed_tensors"] = count
+    stats["packed_bytes"] = sum(sizes)
+    stats["mode"] = "pinned"
+    return {
+        id(t): ("__csp_packed_tensor_v1__", index, j) for j, t in enumerate(tensors)
+    }
+
+
 def _stage_result(result, stats, buffers, buffer_meta):
     """Replace large tensors in ``result`` with out-of-band buffer
     markers.  A large CUDA tensor is only recorded here (device pointer,
     byte count, the tensor as keep-alive); the send loop streams it
     through hipHostMalloc-pinned memory.  Large contiguous CPU tensors
     are shipped zero-copy from their own storage.  Small tensors stay
-    inline in the pickle."""
+    inline in the pickle, unless PACK_RESULTS gathers the small CUDA
+    tensors into one more streamed buffer (_pack_small_cuda)."""
     if "torch" not in sys.modules:
         return result
     import ctypes
@@ -292,6 +412,10 @@ def _stage_result(result, stats, buffers, buffer_meta):
         except Exception:  # noqa: BLE001
             lib = None
 
+    packed = {}
+    if PACK_RESULTS and lib is not None:
+        packed = _pack_small_cuda(lib, result, stats, buffers, buffer_meta)
+
     def emit_buffer(view, keepalive, dtype, shape):
         buffers.append((view, keepalive))
         buffer_meta.append(
@@ -303,6 +427,8 @@ def _stage_result(result, stats, buffers, buffer_meta):
         stats["tensors"] += 1
         nbytes = t.numel() * t.element_size()
         stats["bytes"] += nbytes
+        if id(t) in packed:
+            return packed[id(t)]
         if nbytes < STAGING_THRESHOLD:
             return t.cpu() if t.is_cuda else t
         if t.is_cuda:
@@ -659,6 +785,9 @@ def _serve_one(request):
     if exception is None and result is not None:
         t_stage = time.monotonic()
         stats = {"tensors": 0, "pinned_tensors": 0, "bytes": 0, "mode": "none"}
+        if PACK_RESULTS:
+            stats["packed_tensors"] = 0
+            stats["packed_bytes"] = 0
         try:
             result = _stage_result(result, stats, buffers, meta["buffers"])
             meta["staging"] = stats

@@ -165,11 +165,71 @@ def extract_arg_buffers(args, kwargs, threshold: int, to_device: bool = False):
     return new_args, new_kwargs, buffer_meta, buffers
 
 
+def verify_result_buffers(buffer_meta, buffers) -> int:
+    """Check every received result buffer whose meta entry carries
+    ``"sum": [s0, s1]`` (the worker's on-GPU checksum of the bytes it sent)
+    against ``native_io.checksum`` of the bytes that arrived.  Returns how
+    many were checked: 0 when ``libcsp_io.so`` is not loaded, as on the
+    argument side.  A mismatch raises ``RuntimeError``; the frames have all
+    been consumed by then, so the channel stays usable."""
+    verified = 0
+    for i, info in enumerate(buffer_meta):
+        if "sum" not in info or i >= len(buffers):
+            continue
+        # looked up at call time: None when libcsp_io.so is not loaded
+        sums = native_io.checksum(buffers[i])
+        if sums is None:
+            continue
+        verified += 1
+        got = [int(sums[0]), int(sums[1])]
+        want = [int(info["sum"][0]), int(info["sum"][1])]
+        if got != want:
+            raise RuntimeError(
+                f"result buffer {i} failed its integrity check: the worker "
+                f"sent checksum {want}, the {memoryview(buffers[i]).nbytes} "
+                f"bytes received give {got}"
+            )
+    return verified
+
+
 def _reconstruct(result, buffer_meta, buffers):
     """Replace out-of-band tensor-buffer markers with rebuilt torch
     tensors (workers ship large tensors as raw frames; see
-    remote/worker_template.py protocol note)."""
+    remote/worker_template.py protocol note).
+
+    A packed marker ``("__csp_packed_tensor_v1__", i, j)`` becomes tensor
+    ``j`` of buffer ``i``: a zero-copy ``torch.frombuffer`` view at its
+    ``offset`` into the received buffer.  All tensors of one packed buffer
+    share that buffer, which stays alive as long as any of them does (so one
+    small survivor keeps the whole frame in memory; ``clone()`` it to let
+    go).  Their byte ranges do not overlap.  A marker met twice gives the
+    same tensor object, as the worker had it."""
     import torch
+
+    writable = {}  # buffer index -> the one writable object its views share
+    rebuilt = {}  # (i, j) -> tensor
+
+    def shared(i: int):
+        if i not in writable:
+            raw = buffers[i]
+            writable[i] = bytearray(raw) if isinstance(raw, bytes) else raw
+        return writable[i]
+
+    def build_packed(i: int, j: int):
+        if (i, j) not in rebuilt:
+            info = buffer_meta[i]["packed"][j]
+            dtype = getattr(torch, info["dtype"])
+            count = 1
+            for dim in info["shape"]:
+                count *= int(dim)
+            if count == 0:
+                t = torch.empty(info["shape"], dtype=dtype)
+            else:
+                t = torch.frombuffer(
+                    shared(i), dtype=dtype, count=count, offset=int(info["offset"])
+                ).reshape(info["shape"])
+            rebuilt[(i, j)] = t
+        return rebuilt[(i, j)]
 
     def build(i: int):
         info = buffer_meta[i]
@@ -188,6 +248,13 @@ def _reconstruct(result, buffer_meta, buffers):
             and obj[0] == "__csp_tensor_buffer_v1__"
         ):
             return build(obj[1])
+        if (
+            isinstance(obj, tuple)
+            and len(obj) == 3
+            and isinstance(obj[0], str)
+            and obj[0] == "__csp_packed_tensor_v1__"
+        ):
+            return build_packed(obj[1], obj[2])
         if isinstance(obj, dict):
             return {k: walk(v) for k, v in obj.items()}
         if isinstance(obj, tuple):
@@ -216,6 +283,10 @@ async def run_task(
     the worker's A1 ack arrives — i.e. once user code may have begun.
     On ChannelClosed the caller reads it to decide whether a retry could
     re-execute a partially-run task.
+
+    Result buffers whose meta carries a checksum are verified before any
+    tensor is rebuilt (:func:`verify_result_buffers`); the count goes to
+    ``meta["result_integrity"]``.  A mismatch raises ``RuntimeError``.
     """
     request = cloudpickle.dumps(
         {
@@ -246,9 +317,14 @@ async def run_task(
     )
     assert "value" in parsed, "worker reply ended at the ack frame"
     result_blob, meta, nbuf = parsed["value"]
+    buffer_meta = meta.get("buffers", [])
+    if nbuf and any("sum" in info for info in buffer_meta):
+        meta["result_integrity"] = {
+            "verified": verify_result_buffers(buffer_meta, buffers)
+        }
     result, exception = cloudpickle.loads(result_blob)
     if nbuf:
-        result = _reconstruct(result, meta.get("buffers", []), buffers)
+        result = _reconstruct(result, buffer_meta, buffers)
     return result, exception, meta
 
 

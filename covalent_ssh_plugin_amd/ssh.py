@@ -108,6 +108,16 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # pickle file).  The run_local_on_ssh_fail fallback runs the function
     # with the original CPU tensors.
     "device_tensor_args": False,
+    # The CUDA tensors of a result that are below
+    # pinned_staging_threshold_bytes (a state_dict, a list of gradients)
+    # are gathered on the GPU into one arena and sent as a single streamed
+    # frame with a checksum that the dispatcher verifies, instead of one
+    # pageable copy each inside the pickle.  They come back as views into
+    # one shared buffer.  Needs persistent_workers or isolate_tasks.
+    "pack_tensor_results": False,
+    # Pack only when those tensors total at least this many bytes (below
+    # it the reply is a single small frame anyway).
+    "pack_results_min_bytes": 65536,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -299,6 +309,8 @@ class SSHExecutor(RemoteExecutor):
         isolate_tasks: Optional[bool] = None,
         isolate_preload: str = "",
         device_tensor_args: Optional[bool] = None,
+        pack_tensor_results: Optional[bool] = None,
+        pack_results_min_bytes: Optional[int] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -358,6 +370,17 @@ class SSHExecutor(RemoteExecutor):
                 "device_tensor_args needs persistent_workers or isolate_tasks: "
                 "only the worker channel carries tensor arguments out of band"
             )
+        self.pack_tensor_results = bool(
+            _conf("pack_tensor_results", pack_tensor_results, default=False)
+        )
+        if self.pack_tensor_results and not self.persistent_workers:
+            raise ValueError(
+                "pack_tensor_results needs persistent_workers or isolate_tasks: "
+                "only the worker channel carries result tensors out of band"
+            )
+        self.pack_results_min_bytes = int(
+            _conf("pack_results_min_bytes", pack_results_min_bytes)
+        )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -794,7 +817,13 @@ class SSHExecutor(RemoteExecutor):
 
         digest = hashlib.sha256(Path(local_lib).read_bytes()).hexdigest()[:12]
         remote_lib = f"{self.remote_cache}/lib/csp_gpu-{digest}.so"
-        probe = await transport.run(f"test -f {shlex.quote(remote_lib)}")
+        # mkdir -p here, not left to tar: two endpoints that share a remote
+        # filesystem (two names for one home) provision at the same time,
+        # and concurrent tar extractions race creating the same lib/ dir
+        probe = await transport.run(
+            f"mkdir -p {shlex.quote(self.remote_cache + '/lib')} && "
+            f"test -f {shlex.quote(remote_lib)}"
+        )
         if not probe.ok:
             # publish atomically (rename) so a concurrent stub can never
             # ctypes-load a half-written library
@@ -819,6 +848,8 @@ class SSHExecutor(RemoteExecutor):
             isolate=self.isolate_tasks,
             isolate_preload=self.isolate_preload,
             telemetry_every=self.gpu_telemetry_every,
+            pack_results=self.pack_tensor_results,
+            pack_min_bytes=self.pack_results_min_bytes,
         )
         digest = _script_digest(text)
         key = self._pool_key()
