@@ -58,8 +58,11 @@ class SSHClusterExecutor:
 
     Every other keyword argument goes to each node's :class:`SSHExecutor`
     unchanged (``persistent_workers``, ``device_tensor_args``,
-    ``pack_tensor_results``, ``pack_results_min_bytes``, ...), so the
-    executor's own validation applies per node.
+    ``pack_tensor_results``, ``pack_results_min_bytes``,
+    ``cache_tensor_args``, ``arg_cache_bytes``, ``arg_cache_min_bytes``,
+    ...), so the executor's own validation applies per node.  The argument
+    cache is per worker: an electron that lands on another node, or another
+    GPU slot, stores its tensors there first.
     """
 
     def __init__(

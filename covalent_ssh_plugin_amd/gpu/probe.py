@@ -108,6 +108,13 @@ def load(path: str = "") -> ctypes.CDLL:
     lib.csp_checksum_dev.argtypes = [
         ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
     ]
+    lib.csp_copy_checksum_dev.restype = ctypes.c_int
+    lib.csp_copy_checksum_dev.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+    ]
+    lib.csp_copy_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_copy_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_pack_dev.restype = ctypes.c_int
     lib.csp_pack_dev.argtypes = [
         ctypes.POINTER(ctypes.c_void_p),
@@ -239,6 +246,33 @@ def checksum_device(data_ptr: int, nbytes: int) -> tuple:
     _check(lib, lib.csp_checksum_dev(ctypes.c_void_p(data_ptr), nbytes, out),
            "csp_checksum_dev")
     return int(out[0]), int(out[1])
+
+
+def copy_checksum_device(dst_ptr: int, src_ptr: int, nbytes: int) -> tuple:
+    """Copy ``nbytes`` from device pointer ``src_ptr`` to device pointer
+    ``dst_ptr`` and return ``(s0, s1)`` of those bytes, the same two numbers
+    as :func:`checksum_device`, from one pass over HBM (``cache_tensor_args``:
+    a cached master's private copy for one electron).  Both pointers must be
+    16-byte aligned and the ranges disjoint; a violation raises
+    ``GpuLibError`` and launches nothing.  Runs on the library's copy stream;
+    work on the two buffers on another stream must be complete
+    (``torch.cuda.synchronize()``) first."""
+    lib = load()
+    out = (ctypes.c_uint64 * 2)()
+    _check(
+        lib,
+        lib.csp_copy_checksum_dev(
+            ctypes.c_void_p(dst_ptr), ctypes.c_void_p(src_ptr), nbytes, out
+        ),
+        "csp_copy_checksum_dev",
+    )
+    return int(out[0]), int(out[1])
+
+
+def copy_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`copy_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_copy_checksum_grid_cap(int(cap)))
 
 
 PACK_ALIGN = 16  # every packed segment starts on a multiple of this

@@ -70,6 +70,7 @@ def render_worker(
     telemetry_every: int = 0,
     pack_results: bool = False,
     pack_min_bytes: int = 0,
+    arg_cache_bytes: int = 0,
 ) -> str:
     """Return the persistent worker script text (one per endpoint; the
     GPU slot arrives via the CSP_GPU_SLOT env var at launch).  With
@@ -77,7 +78,9 @@ def render_worker(
     in a freshly forked child process; ``isolate_preload`` picks what
     the zygote imports pre-fork ("torch" or "none").  ``pack_results``
     makes the worker send the small CUDA tensors of a result as one packed
-    frame when they total at least ``pack_min_bytes``."""
+    frame when they total at least ``pack_min_bytes``.  ``arg_cache_bytes``
+    is the worker's budget for repeated tensor arguments kept in HBM
+    (``cache_tensor_args``); 0 means no cache."""
     text = _template_text(str(_WORKER_TEMPLATE_PATH))
     thr = DEFAULT_STAGING_THRESHOLD if staging_threshold is None else int(staging_threshold)
     replacements = {
@@ -91,6 +94,7 @@ def render_worker(
         "__CSP_TELEMETRY_EVERY__": str(int(telemetry_every)),
         "__CSP_PACK_RESULTS__": repr(bool(pack_results)),
         "__CSP_PACK_MIN_BYTES__": str(int(pack_min_bytes)),
+        "__CSP_ARG_CACHE_BYTES__": str(int(arg_cache_bytes)),
     }
     for token, value in replacements.items():
         text = text.replace(token, value)

@@ -27,8 +27,17 @@ Protocol (all frames: 8-byte big-endian length + payload):
              chunk's H2D copy running while the next is read, and the
              electron gets a CUDA tensor.  When the entry carries
              "sum": [s0, s1], csp_checksum_dev recomputes the checksum
-             over the bytes in HBM and a mismatch fails the task.
-  ack      = pickle tuple ("A1", op_id) — written as soon as the request
+             over the bytes in HBM and a mismatch fails the task.  With
+             the executor option cache_tensor_args an entry may also carry
+             "cache": {"key", "store": true} (its frame lands in a master
+             buffer that stays in HBM under the key, and the electron's
+             tensor is a copy made and checksummed in one pass by
+             csp_copy_checksum_dev) or {"key", "ref": true} (NO frame: the
+             tensor is such a copy of the master already held; when the
+             key is gone, or the checksum of the copy is not "sum", the
+             argument fails, meta["arg_cache"]["miss"] names the entry and
+             the dispatcher sends the task again with full frames).
+  ack     = pickle tuple ("A1", op_id) — written as soon as the request
              (and its arg frames) has been fully received, BEFORE any
              user code runs.  The dispatcher uses it to distinguish
              "worker died before starting the task" (safe to retry on a
@@ -61,6 +70,7 @@ corrupt frames.
 """
 
 
+import collections
 import json
 import os
 import struct
@@ -78,6 +88,9 @@ IDLE_TIMEOUT = float(__CSP_IDLE_TIMEOUT__)  # seconds; 0 = never exit
 # total at least PACK_MIN_BYTES.
 PACK_RESULTS = bool(__CSP_PACK_RESULTS__)
 PACK_MIN_BYTES = int(__CSP_PACK_MIN_BYTES__)
+# Budget in bytes for the masters of repeated tensor arguments kept in HBM
+# (executor option cache_tensor_args); 0 = no cache.
+ARG_CACHE_BYTES = int(__CSP_ARG_CACHE_BYTES__)
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
 # break the children) and every electron executes in a freshly forked
@@ -199,6 +212,13 @@ def _load_gpu_lib():
     ]
     lib.csp_checksum_dev.restype = ctypes.c_int
     lib.csp_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+    ]
+    lib.csp_copy_checksum_dev.restype = ctypes.c_int
+    lib.csp_copy_checksum_dev.argtypes = [
+        ctypes.c_void_p,
         ctypes.c_void_p,
         ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_uint64),
@@ -557,7 +577,10 @@ def _verify_device_arg(lib, index, tensor, nbytes, info, stage):
             % (index, lib.csp_last_error().decode(errors="replace"))
         )
     stage["verified"] += 1
-    got = [int(out[0]), int(out[1])]
+    _compare_arg_sum(index, [int(out[0]), int(out[1])], info, nbytes)
+
+
+def _compare_arg_sum(index, got, info, nbytes):
     want = [int(info["sum"][0]), int(info["sum"][1])]
     if got != want:
         raise RuntimeError(
@@ -567,17 +590,140 @@ def _verify_device_arg(lib, index, tensor, nbytes, info, stage):
         )
 
 
-def _receive_device_arg(index, info, stage):
+# --- repeated tensor arguments kept in HBM (cache_tensor_args) --------------
+#
+# key -> (master, nbytes, [s0, s1]); least recently used first.  A master is
+# a uint8 CUDA tensor that only this file touches: every electron gets a
+# private copy made (and verified) by csp_copy_checksum_dev.
+
+_arg_cache = collections.OrderedDict()
+_arg_cache_resident = 0  # bytes held by the masters
+
+
+def _new_arg_cache_report():
+    return {"hits": [], "stored": [], "not_stored": [], "miss": [], "evicted": []}
+
+
+def _arg_cache_drop(key, report=None):
+    global _arg_cache_resident
+    entry = _arg_cache.pop(key, None)
+    if entry is not None:
+        _arg_cache_resident -= entry[1]
+        if report is not None:
+            report["evicted"].append(key)
+
+
+def _arg_cache_evict_all(report, keep=None):
+    """Let go of every master but ``keep`` and return their memory to the
+    device.  Returns whether anything was let go."""
+    import torch
+
+    victims = [k for k in _arg_cache if k != keep]
+    for k in victims:
+        _arg_cache_drop(k, report)
+    if victims:
+        torch.cuda.empty_cache()
+    return bool(victims)
+
+
+def _arg_cache_new_master(nbytes, report):
+    """A master of ``nbytes`` within ARG_CACHE_BYTES, least recently used
+    entries evicted to make room; None when it does not fit the budget or
+    the device has no room for it."""
+    import torch
+
+    if nbytes > ARG_CACHE_BYTES:
+        return None
+    while _arg_cache and _arg_cache_resident + nbytes > ARG_CACHE_BYTES:
+        _arg_cache_drop(next(iter(_arg_cache)), report)
+    try:
+        return torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    except Exception:  # noqa: BLE001 - out of HBM: the argument goes uncached
+        return None
+
+
+def _alloc_device_arg(info, dtype, report, keep=None):
+    """The electron's own tensor.  When the device has no room, the masters
+    (all but ``keep``) go and the allocation is tried once more."""
+    import torch
+
+    try:
+        return torch.empty(info["shape"], dtype=dtype, device="cuda")
+    except Exception:  # noqa: BLE001 - e.g. out of HBM
+        if not _arg_cache_evict_all(report, keep=keep):
+            raise
+    return torch.empty(info["shape"], dtype=dtype, device="cuda")
+
+
+def _copy_from_master(lib, index, tensor, master, nbytes):
+    """csp_copy_checksum_dev(master -> tensor); returns [s0, s1]."""
+    import ctypes
+
+    out = (ctypes.c_uint64 * 2)()
+    rc = lib.csp_copy_checksum_dev(
+        ctypes.c_void_p(tensor.data_ptr()), ctypes.c_void_p(master.data_ptr()),
+        nbytes, out,
+    )
+    if rc != 0:
+        raise RuntimeError(
+            "argument buffer %d: csp_copy_checksum_dev failed: %s"
+            % (index, lib.csp_last_error().decode(errors="replace"))
+        )
+    return [int(out[0]), int(out[1])]
+
+
+def _device_arg_from_cache(lib, index, info, dtype, nbytes, key, stage, report):
+    """A ``ref`` entry: no frame on the wire, the tensor is a verified copy
+    of the cached master.  An absent key, another byte count or another
+    checksum is a miss: the entry goes, the index is reported, and the
+    argument fails with an error that the dispatcher answers by sending the
+    task again with full frames."""
+    entry = _arg_cache.get(key)
+    reason = None
+    if entry is None:
+        reason = "is not in the cache"
+    elif entry[1] != nbytes or "sum" not in info:
+        reason = "holds %d bytes, the argument has %d" % (entry[1], nbytes)
+    else:
+        tensor = _alloc_device_arg(info, dtype, report, keep=key)
+        got = _copy_from_master(lib, index, tensor, entry[0], nbytes)
+        want = [int(info["sum"][0]), int(info["sum"][1])]
+        if got == want:
+            _arg_cache.move_to_end(key)
+            report["hits"].append(key)
+            stage["tensors"] += 1
+            stage["verified"] += 1
+            if stage["mode"] == "none":
+                stage["mode"] = "cached"
+            return tensor
+        reason = "has checksum %r, the dispatcher sent %r" % (got, want)
+    _arg_cache_drop(key)
+    report["miss"].append(index)
+    raise RuntimeError(
+        "argument buffer %d: cached argument %s %s" % (index, key, reason)
+    )
+
+
+def _receive_device_arg(index, info, stage, report):
     """Persistent mode: take argument frame ``index`` off stdin straight
     into a fresh CUDA tensor.  Whatever goes wrong short of a broken
     stream, the frame is consumed before the error is raised, so the
-    caller can go on to the next frame and report the error in R1."""
+    caller can go on to the next frame and report the error in R1.
+
+    With ``"cache": {"key", "ref": true}`` there is no frame: the tensor is
+    copied from the cached master (_device_arg_from_cache).  With
+    ``"cache": {"key", "store": true}`` the frame lands in a new master
+    first and the tensor is a verified copy of it; when the key is already
+    cached, or the master does not fit, the frame lands in the tensor as
+    without a cache."""
+    global _arg_cache_resident
     import ctypes
 
+    cache = info.get("cache") or {}
     try:
         lib = _device_arg_lib()
     except RuntimeError:
-        if _read_frame(0) is None:  # drain with the Python reader
+        if not cache.get("ref") and _read_frame(0) is None:  # drain with the Python reader
             os._exit(4)
         raise
     import torch
@@ -586,15 +732,44 @@ def _receive_device_arg(index, info, stage):
     nbytes = torch.empty((), dtype=dtype).element_size()
     for dim in info["shape"]:
         nbytes *= int(dim)
-    alloc_error = None
-    tensor = None
     # the library's copy stream does not wait on the null stream
     torch.cuda.synchronize()
+    if cache.get("ref"):
+        return _device_arg_from_cache(
+            lib, index, info, dtype, nbytes, cache["key"], stage, report
+        )
+    key = None
+    master = None
+    if cache.get("store") and "sum" in info and nbytes:
+        key = cache["key"]
+        if key in _arg_cache:
+            # the frame is on its way all the same: it lands in the tensor
+            _arg_cache.move_to_end(key)
+            report["stored"].append(key)
+            key = None
+        else:
+            master = _arg_cache_new_master(nbytes, report)
+            if master is None:
+                report["not_stored"].append(key)
+    alloc_error = None
+    tensor = None
     try:
-        tensor = torch.empty(info["shape"], dtype=dtype, device="cuda")
+        tensor = _alloc_device_arg(info, dtype, report)
     except Exception as e:  # noqa: BLE001 - e.g. out of HBM
         alloc_error = e  # drain mode below: the frame still has to go
+        if master is not None:
+            # the new master goes too: the argument travels uncached
+            master = None
+            report["not_stored"].append(key)
+            torch.cuda.empty_cache()
+            try:
+                tensor = torch.empty(info["shape"], dtype=dtype, device="cuda")
+                alloc_error = None
+            except Exception as e2:  # noqa: BLE001
+                alloc_error = e2
     ptr = tensor.data_ptr() if (tensor is not None and nbytes) else 0
+    if master is not None:
+        ptr = master.data_ptr()
     read_ms = ctypes.c_double()
     h2d_ms = ctypes.c_double()
     rc = lib.csp_h2d_stream_fd(
@@ -622,13 +797,23 @@ def _receive_device_arg(index, info, stage):
     stage["mode"] = "pinned-h2d"
     stage["tensors"] += 1
     stage["bytes"] += nbytes
-    _verify_device_arg(lib, index, tensor, nbytes, info, stage)
+    if master is None:
+        _verify_device_arg(lib, index, tensor, nbytes, info, stage)
+        return tensor
+    # the copy that the electron gets is also the verification pass
+    got = _copy_from_master(lib, index, tensor, master, nbytes)
+    stage["verified"] += 1
+    _compare_arg_sum(index, got, info, nbytes)  # a mismatch drops the master
+    _arg_cache[key] = (master, nbytes, got)
+    _arg_cache_resident += nbytes
+    report["stored"].append(key)
     return tensor
 
 
 def _receive_arg_frames(arg_meta):
     """Read the request's out-of-band argument frames.  Returns
-    (frames, stage, error); frames is None when stdin ended.  A frame is a
+    (frames, stage, error, cache_report); frames is None when stdin ended,
+    cache_report is None unless an entry carries ``"cache"``.  A frame is a
     bytearray (host) or, for a device entry in persistent mode, the CUDA
     tensor itself.  The first per-argument error is kept and EVERY frame
     is still consumed, so the stream stays aligned.
@@ -639,10 +824,17 @@ def _receive_arg_frames(arg_meta):
     frames = []
     stage = _new_arg_stage()
     error = None
+    report = None
+    if any(info.get("cache") for info in arg_meta):
+        report = _new_arg_cache_report()
     for index, info in enumerate(arg_meta):
         if info.get("device") and not ISOLATE:
             try:
-                frames.append(_receive_device_arg(index, info, stage))
+                frames.append(
+                    _receive_device_arg(
+                        index, info, stage, report or _new_arg_cache_report()
+                    )
+                )
             except Exception as e:  # noqa: BLE001
                 frames.append(None)
                 if error is None:
@@ -650,9 +842,12 @@ def _receive_arg_frames(arg_meta):
             continue
         f = _read_frame(0)
         if f is None:
-            return None, stage, error
+            return None, stage, error, report
         frames.append(bytearray(f))
-    return frames, stage, error
+    if report is not None:
+        report["entries"] = len(_arg_cache)
+        report["resident_bytes"] = _arg_cache_resident
+    return frames, stage, error, report
 
 
 def _device_args_in_child(frames, meta_list, stage):
@@ -730,6 +925,8 @@ def _serve_one(request):
             "pid": os.getpid(), "worker": True, "served": _served}
     arg_stage = request.get("_arg_staging") or _new_arg_stage()
     meta["arg_staging"] = arg_stage
+    if request.get("_arg_cache") is not None:
+        meta["arg_cache"] = request["_arg_cache"]
     result = None
     exception = None
     buffers = []
@@ -928,11 +1125,12 @@ def main():
         request = pickle.loads(frame)
         arg_meta = request.get("arg_buffers") or []
         if arg_meta:
-            frames, arg_stage, arg_error = _receive_arg_frames(arg_meta)
+            frames, arg_stage, arg_error, cache_report = _receive_arg_frames(arg_meta)
             if frames is None:
                 return
             request["_arg_buffer_frames"] = frames
             request["_arg_staging"] = arg_stage
+            request["_arg_cache"] = cache_report
             request["_arg_error"] = arg_error
         # ack AFTER the full request is in hand, BEFORE user code runs:
         # the dispatcher's retry-on-death policy keys off this frame

@@ -14,8 +14,14 @@ same host share workers, mirroring the transport pool and slot tables.
 from __future__ import annotations
 
 import asyncio
+import hashlib
+import os
+import struct
+import threading
+import weakref
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Set, Tuple
 
 import cloudpickle
 
@@ -31,6 +37,10 @@ class WorkerHandle:
     channel: Channel
     startup_meta: dict
     key: WorkerKey
+    #: content keys of the tensor arguments this worker is believed to hold
+    #: in HBM (``cache_tensor_args``).  A new handle starts empty, so a
+    #: worker that died or was respawned is assumed to hold nothing.
+    resident: Set[str] = field(default_factory=set)
 
     @property
     def alive(self) -> bool:
@@ -104,12 +114,129 @@ async def get_worker(key: WorkerKey, launcher, startup_timeout: float = 180.0) -
         return handle
 
 
-def extract_arg_buffers(args, kwargs, threshold: int, to_device: bool = False):
+# --- content identity of cached tensor arguments ----------------------------
+#
+# The (s0, s1) checksum is linear: adding +1, -2, +1 to three neighbouring
+# words changes neither sum.  It guards the transfer, but it cannot say
+# which bytes a cache entry holds; that is the job of a cryptographic digest.
+
+ARG_CACHE_CHUNK = 8 << 20  # bytes per chunk digest and per checksum piece
+_HASH_THREADS_MAX = 8
+_hash_pool: Optional[ThreadPoolExecutor] = None
+_hash_pool_lock = threading.Lock()
+
+
+def hash_threads() -> int:
+    return max(1, min(_HASH_THREADS_MAX, os.cpu_count() or 1))
+
+
+def _pool() -> ThreadPoolExecutor:
+    global _hash_pool
+    with _hash_pool_lock:
+        if _hash_pool is None:
+            _hash_pool = ThreadPoolExecutor(
+                max_workers=hash_threads(), thread_name_prefix="csp-hash"
+            )
+        return _hash_pool
+
+
+def _chunks(nbytes: int, chunk_bytes: int):
+    return [(off, min(chunk_bytes, nbytes - off)) for off in range(0, nbytes, chunk_bytes)]
+
+
+def _map(fn, pieces, threads: Optional[int]):
+    if len(pieces) <= 1 or threads == 1:
+        return [fn(p) for p in pieces]
+    if threads is None:
+        return list(_pool().map(fn, pieces))
+    with ThreadPoolExecutor(max_workers=threads) as pool:  # measurements only
+        return list(pool.map(fn, pieces))
+
+
+def content_key(buf, chunk_bytes: int = ARG_CACHE_CHUNK, threads: Optional[int] = None) -> str:
+    """The cache identity of ``buf``'s bytes: the 16-byte blake2b digest, in
+    hex, over the byte count (8 bytes, little endian) followed by the 16-byte
+    blake2b digests of its ``chunk_bytes`` chunks in order.  The chunk
+    digests are computed on a small thread pool (hashlib releases the GIL).
+    The key covers bytes only: two tensors with equal bytes and another dtype
+    or shape share it."""
+    view = memoryview(buf).cast("B")
+    nbytes = view.nbytes
+
+    def digest(piece):
+        off, n = piece
+        return hashlib.blake2b(view[off : off + n], digest_size=16).digest()
+
+    outer = hashlib.blake2b(struct.pack("<Q", nbytes), digest_size=16)
+    for d in _map(digest, _chunks(nbytes, chunk_bytes), threads):
+        outer.update(d)
+    return outer.hexdigest()
+
+
+def threaded_checksum(buf, chunk_bytes: int = ARG_CACHE_CHUNK, threads: Optional[int] = None):
+    """``native_io.checksum(buf)``, bit for bit, composed from the sums of
+    ``chunk_bytes`` pieces computed on the thread pool (ctypes releases the
+    GIL).  For a piece that starts at word ``o``: ``s0 = sum s0_c`` and
+    ``s1 = sum (s1_c + (o mod 2^32) * s0_c)`` modulo 2^64.  ``chunk_bytes``
+    is a power of two that divides 16 GiB, so no piece crosses a 2^32-word
+    boundary, where the weight wraps, and only the last piece can have a
+    length that is no multiple of 4.  ``None`` when ``libcsp_io.so`` is not
+    loaded."""
+    if chunk_bytes < 4 or chunk_bytes & (chunk_bytes - 1) or chunk_bytes > (16 << 30):
+        raise ValueError("chunk_bytes must be a power of two between 4 and 16 GiB")
+    if native_io.load() is None:
+        return None
+    view = memoryview(buf).cast("B")
+    pieces = _chunks(view.nbytes, chunk_bytes)
+    if len(pieces) <= 1:
+        return native_io.checksum(view)
+    mask = (1 << 64) - 1
+    s0 = s1 = 0
+    sums = _map(lambda p: native_io.checksum(view, p[1], p[0]), pieces, threads)
+    for (off, _n), (c0, c1) in zip(pieces, sums):
+        s0 += c0
+        s1 += c1 + ((off // 4) % (1 << 32)) * c0
+    return s0 & mask, s1 & mask
+
+
+_key_memo: Dict[int, tuple] = {}  # id(tensor) -> (weakref, guard, key)
+
+
+def tensor_content_key(tensor, view) -> str:
+    """:func:`content_key` of ``view``, the contiguous bytes of ``tensor``,
+    remembered per tensor object for as long as it lives and its
+    ``(data_ptr, nbytes, dtype, _version)`` stay the same: hashing is the
+    largest dispatcher cost of a cache hit.  Memory changed behind torch's
+    back leaves a stale key; the checksum, computed afresh on every dispatch
+    and compared by the worker on every hit, then turns the hit into a miss."""
+    guard = (tensor.data_ptr(), len(view), tensor.dtype, tensor._version)
+    ident = id(tensor)
+    memo = _key_memo.get(ident)
+    if memo is not None and memo[0]() is tensor and memo[1] == guard:
+        return memo[2]
+    key = content_key(view)
+    ref = weakref.ref(tensor, lambda _r, ident=ident: _key_memo.pop(ident, None))
+    _key_memo[ident] = (ref, guard, key)
+    return key
+
+
+def extract_arg_buffers(
+    args, kwargs, threshold: int, to_device: bool = False,
+    cache_min_bytes: Optional[int] = None,
+):
     """Pull large contiguous CPU torch tensors out of (args, kwargs) and
     replace them with out-of-band buffer markers (the request-direction
     mirror of the worker's result staging).  Returns
     (new_args, new_kwargs, buffer_meta, buffers); no-op (and no torch
     import) unless torch is already loaded in the dispatcher.
+
+    ``cache_min_bytes`` (the executor's ``cache_tensor_args``; ``None`` is
+    off) with ``to_device``: a tensor of at least that many bytes also
+    carries ``"cache": {"key": <hex>}``, its :func:`content_key`, and its
+    checksum comes from :func:`threaded_checksum`.  :func:`run_task` decides
+    per worker whether the bytes or only the key travel.  Without
+    ``libcsp_io.so`` there is no checksum and so no cache entry: a hit could
+    not be verified.
 
     ``to_device`` (the executor's ``device_tensor_args``): EVERY CPU tensor
     is extracted whatever its size, so an electron never gets a mix of CPU
@@ -137,10 +264,13 @@ def extract_arg_buffers(args, kwargs, threshold: int, to_device: bool = False):
         info = {"dtype": str(src_t.dtype).replace("torch.", ""), "shape": list(src_t.shape)}
         if to_device:
             info["device"] = True
+            cacheable = cache_min_bytes is not None and nbytes >= max(1, cache_min_bytes)
             # looked up at call time: None when libcsp_io.so is not loaded
-            sums = native_io.checksum(view)
+            sums = threaded_checksum(view) if cacheable else native_io.checksum(view)
             if sums is not None:
                 info["sum"] = [int(sums[0]), int(sums[1])]
+                if cacheable:
+                    info["cache"] = {"key": tensor_content_key(t, view)}
         buffer_meta.append(info)
         return ("__csp_tensor_buffer_v1__", len(buffers) - 1)
 
@@ -267,6 +397,63 @@ def _reconstruct(result, buffer_meta, buffers):
     return walk(result)
 
 
+class _ArgCacheSend:
+    """The ``cache_tensor_args`` side of one :func:`run_task`: which cached
+    entries travel as a reference, decided while the request is being sent,
+    and what the worker's report means for ``handle.resident``."""
+
+    def __init__(self, handle, base, entries, views, cache_stats):
+        self.handle = handle
+        self.base = base
+        self.entries = entries
+        self.views = views
+        self.cache_stats = cache_stats
+        self.keys = [(info.get("cache") or {}).get("key") for info in entries]
+        self.refs = [False] * len(entries)
+
+    def frames(self, full: bool):
+        """The request's frames.  A generator: the channel runs it frame by
+        frame under its write lock, so the decisions are taken in send
+        order.  ``full``: no references, every entry with its frame."""
+        resident = self.handle.resident
+        self.refs = [
+            key is not None and not full and key in resident for key in self.keys
+        ]
+        wire = []
+        for info, key, ref in zip(self.entries, self.keys, self.refs):
+            if key is not None:
+                info = dict(info)
+                info["cache"] = {"key": key, "ref" if ref else "store": True}
+            wire.append(info)
+        yield cloudpickle.dumps(dict(self.base, arg_buffers=wire))
+        for view, key, ref in zip(self.views, self.keys, self.refs):
+            if ref:
+                continue
+            yield view
+            if key is not None:
+                resident.add(key)  # its frame has been written
+
+    def reconcile(self, meta) -> bool:
+        """Bring ``handle.resident`` in line with the worker's report and
+        count; returns whether the worker missed a reference."""
+        report = meta.get("arg_cache") or {}
+        held = set(report.get("stored") or ()) | set(report.get("hits") or ())
+        for key in self.keys:
+            if key is not None and key not in held:
+                self.handle.resident.discard(key)
+        missed = [i for i in (report.get("miss") or ()) if 0 <= i < len(self.keys)]
+        stats = self.cache_stats
+        if stats is not None:
+            for view, key, ref in zip(self.views, self.keys, self.refs):
+                if ref and key in held:
+                    stats["arg_cache_hits"] = stats.get("arg_cache_hits", 0) + 1
+                    stats["arg_cache_bytes_saved"] = (
+                        stats.get("arg_cache_bytes_saved", 0) + memoryview(view).nbytes
+                    )
+            stats["arg_cache_misses"] = stats.get("arg_cache_misses", 0) + len(missed)
+        return bool(missed)
+
+
 async def run_task(
     handle: WorkerHandle,
     op_id: str,
@@ -276,6 +463,7 @@ async def run_task(
     arg_buffer_meta=None,
     arg_buffers=None,
     ack_state: Optional[dict] = None,
+    cache_stats: Optional[dict] = None,
 ):
     """One electron through a worker.  Returns (result, exception, meta).
 
@@ -287,16 +475,39 @@ async def run_task(
     Result buffers whose meta carries a checksum are verified before any
     tensor is rebuilt (:func:`verify_result_buffers`); the count goes to
     ``meta["result_integrity"]``.  A mismatch raises ``RuntimeError``.
+
+    Argument entries that carry ``"cache": {"key"}`` (``cache_tensor_args``)
+    are decided while the request is being sent, under the channel's write
+    lock and so in send order: a key in ``handle.resident`` travels as
+    ``{"key", "ref": true}`` with no frame, any other as
+    ``{"key", "store": true}`` with its frame, and is resident from the
+    moment that frame has been written, so electrons queued behind it on
+    this worker already refer to it.  The worker's ``meta["arg_cache"]``
+    reconciles the set.  When it reports a miss, user code has not run: the
+    task is sent once more with full frames.  ``cache_stats`` (a mutable
+    dict, the executor's counters) gets ``arg_cache_hits``,
+    ``arg_cache_misses`` and ``arg_cache_bytes_saved``.
     """
-    request = cloudpickle.dumps(
-        {
-            "op_id": op_id,
-            "workdir": workdir,
-            "function_blob": function_blob,
-            "arg_buffers": arg_buffer_meta or [],
-        }
-    )
-    frames = [request] + [view for view, _keep in (arg_buffers or [])]
+    entries = arg_buffer_meta or []
+    cache = None
+    if entries and any("cache" in info for info in entries):
+        cache = _ArgCacheSend(
+            handle,
+            {"op_id": op_id, "workdir": workdir, "function_blob": function_blob},
+            entries,
+            [view for view, _keep in (arg_buffers or [])],
+            cache_stats,
+        )
+    else:
+        request = cloudpickle.dumps(
+            {
+                "op_id": op_id,
+                "workdir": workdir,
+                "function_blob": function_blob,
+                "arg_buffers": entries,
+            }
+        )
+        frames = [request] + [view for view, _keep in (arg_buffers or [])]
     parsed = {}
 
     def reply_frames(main: bytes):
@@ -310,13 +521,29 @@ async def run_task(
         parsed["value"] = (result_blob, meta, nbuf)
         return nbuf
 
-    # pipelined: the channel's write lock is held only while sending, so
-    # queued electrons on one worker overlap their wire round trips
-    _main, buffers = await handle.channel.exchange(
-        frames, reply_frames, timeout=timeout
-    )
-    assert "value" in parsed, "worker reply ended at the ack frame"
-    result_blob, meta, nbuf = parsed["value"]
+    resent = False
+    while True:
+        # pipelined: the channel's write lock is held only while sending, so
+        # queued electrons on one worker overlap their wire round trips
+        _main, buffers = await handle.channel.exchange(
+            frames if cache is None else cache.frames(full=resent),
+            reply_frames,
+            timeout=timeout,
+        )
+        assert "value" in parsed, "worker reply ended at the ack frame"
+        result_blob, meta, nbuf = parsed.pop("value")
+        if cache is None:
+            break
+        missed = cache.reconcile(meta)
+        if resent:
+            meta.setdefault("arg_cache", {})["resent"] = True
+        if resent or not missed:
+            break
+        # the worker no longer holds what a reference named.  It ran no user
+        # code, so the task goes once more, every argument with its frame
+        resent = True
+        if ack_state is not None:
+            ack_state["started"] = False
     buffer_meta = meta.get("buffers", [])
     if nbuf and any("sum" in info for info in buffer_meta):
         meta["result_integrity"] = {

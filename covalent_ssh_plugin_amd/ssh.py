@@ -118,6 +118,24 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # Pack only when those tensors total at least this many bytes (below
     # it the reply is a single small frame anyway).
     "pack_results_min_bytes": 65536,
+    # With device_tensor_args on persistent workers: a worker keeps the
+    # tensor arguments it has received in HBM, keyed by a digest of their
+    # bytes, and the dispatcher sends a repeated argument (the same weights
+    # or dataset fanned out to many electrons) as that key alone.  Every
+    # electron still gets a private CUDA tensor, copied from the cached
+    # master and verified against a fresh checksum in one pass over HBM.
+    # Not with isolate_tasks: the zygote may not touch HIP and its children
+    # do not outlive a task.
+    "cache_tensor_args": False,
+    # Per-worker budget in bytes for the cached masters (8 GiB is under 3 %
+    # of one MI355X's HBM); least recently used entries go first.
+    "arg_cache_bytes": 8 << 30,
+    # Tensors below this many bytes travel as without a cache.  16 MiB is
+    # the smallest measured size at which every kind of hit beat the
+    # dispatch without the cache (profiles/arg_cache.md): from 1 MiB a hit
+    # on the same tensor object already does, but a hit on an equal tensor
+    # that is another object pays the content hash again and does not.
+    "arg_cache_min_bytes": 16 << 20,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -311,6 +329,9 @@ class SSHExecutor(RemoteExecutor):
         device_tensor_args: Optional[bool] = None,
         pack_tensor_results: Optional[bool] = None,
         pack_results_min_bytes: Optional[int] = None,
+        cache_tensor_args: Optional[bool] = None,
+        arg_cache_bytes: Optional[int] = None,
+        arg_cache_min_bytes: Optional[int] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -381,6 +402,31 @@ class SSHExecutor(RemoteExecutor):
         self.pack_results_min_bytes = int(
             _conf("pack_results_min_bytes", pack_results_min_bytes)
         )
+        self.cache_tensor_args = bool(
+            _conf("cache_tensor_args", cache_tensor_args, default=False)
+        )
+        if self.cache_tensor_args and self.isolate_tasks:
+            raise ValueError(
+                "cache_tensor_args cannot be combined with isolate_tasks: the "
+                "zygote may not touch HIP, and the forked children that do "
+                "hold the tensors do not outlive a task"
+            )
+        if self.cache_tensor_args and not (
+            self.device_tensor_args and self.persistent_workers
+        ):
+            raise ValueError(
+                "cache_tensor_args needs device_tensor_args=True and "
+                "persistent_workers=True: the cache holds tensor arguments in "
+                "the HBM of a worker that outlives the task"
+            )
+        self.arg_cache_bytes = int(_conf("arg_cache_bytes", arg_cache_bytes))
+        self.arg_cache_min_bytes = int(
+            _conf("arg_cache_min_bytes", arg_cache_min_bytes)
+        )
+        if self.cache_tensor_args and self.arg_cache_bytes <= 0:
+            raise ValueError("arg_cache_bytes must be positive with cache_tensor_args")
+        if self.cache_tensor_args and self.arg_cache_min_bytes < 0:
+            raise ValueError("arg_cache_min_bytes must not be negative")
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -416,6 +462,12 @@ class SSHExecutor(RemoteExecutor):
             "worker_respawns": 0,
             "cancellations": 0,
             "ssh_failures": 0,
+            # cache_tensor_args: arguments sent as a key alone, references
+            # the worker no longer held (each costs one resend), and the
+            # argument bytes that did not travel
+            "arg_cache_hits": 0,
+            "arg_cache_misses": 0,
+            "arg_cache_bytes_saved": 0,
         }
 
     # ------------------------------------------------------------------
@@ -850,6 +902,7 @@ class SSHExecutor(RemoteExecutor):
             telemetry_every=self.gpu_telemetry_every,
             pack_results=self.pack_tensor_results,
             pack_min_bytes=self.pack_results_min_bytes,
+            arg_cache_bytes=self.arg_cache_bytes if self.cache_tensor_args else 0,
         )
         digest = _script_digest(text)
         key = self._pool_key()
@@ -943,6 +996,7 @@ class SSHExecutor(RemoteExecutor):
                         arg_buffer_meta=arg_meta,
                         arg_buffers=arg_bufs,
                         ack_state=ack_state,
+                        cache_stats=self.counters,
                     )
                 except asyncio.TimeoutError:
                     # the worker is wedged on this task: kill it so the
@@ -1240,6 +1294,11 @@ class SSHExecutor(RemoteExecutor):
                         worker_pool.extract_arg_buffers(
                             args, kwargs, self.pinned_staging_threshold_bytes,
                             to_device=self.device_tensor_args,
+                            cache_min_bytes=(
+                                self.arg_cache_min_bytes
+                                if self.cache_tensor_args
+                                else None
+                            ),
                         )
                     )
                     function_blob = cloudpickle.dumps((function, s_args, s_kwargs))
