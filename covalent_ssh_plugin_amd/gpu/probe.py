@@ -12,7 +12,10 @@ gfx950 only) provides:
   between device memory and a channel fd, the copy overlapped with the I/O,
 * ``csp_checksum_dev`` — the argument checksum over bytes in HBM,
 * ``csp_pack_dev`` — many small device buffers gathered into one contiguous
-  zero-padded arena by one kernel launch (``pack_tensor_results``).
+  zero-padded arena by one kernel launch (``pack_tensor_results``),
+* ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
+  caller's buffers, and ``csp_checksum_grid_cap`` /
+  ``csp_copy_checksum_grid_cap`` (tools and tests only).
 
 On a GPU box these bindings FAIL LOUDLY if the extension is missing or
 broken — there is no eager/CPU fallback for the device path.
@@ -115,6 +118,14 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_copy_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_copy_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_set_sweep_variant.restype = None
+    lib.csp_set_sweep_variant.argtypes = [ctypes.c_int]
+    lib.csp_hbm_sweep_dev.restype = ctypes.c_int
+    lib.csp_hbm_sweep_dev.argtypes = [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+    ]
     lib.csp_pack_dev.restype = ctypes.c_int
     lib.csp_pack_dev.argtypes = [
         ctypes.POINTER(ctypes.c_void_p),
@@ -273,6 +284,41 @@ def copy_checksum_grid_cap(cap: int = 0) -> int:
     """Tools only: set the grid cap of :func:`copy_checksum_device` (0
     restores the shipped default).  Returns the cap in effect."""
     return int(load().csp_copy_checksum_grid_cap(int(cap)))
+
+
+def checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`checksum_device` (0 restores
+    the shipped default of 1024 blocks).  Returns the cap in effect."""
+    return int(load().csp_checksum_grid_cap(int(cap)))
+
+
+SWEEP_VARIANT_DEFAULT = 2
+# float4 vectors in flight per lane for each sweep variant; any other
+# variant number runs variant 0
+SWEEP_UNROLL = {0: 1, 1: 4, 2: 1, 3: 4, 4: 8}
+
+
+def set_sweep_variant(variant: int = SWEEP_VARIANT_DEFAULT) -> None:
+    """Tools only: the HBM sweep variant that the probe, the warm-up and
+    ``hbm_sweep_device(-1, ...)`` run from now on."""
+    load().csp_set_sweep_variant(int(variant))
+
+
+def hbm_sweep_device(variant: int, src_ptr: int, dst_ptr: int, n4: int, blocks: int = 1024) -> None:
+    """One launch of the probe's HBM sweep kernel: ``n4`` 16-byte vectors
+    from device pointer ``src_ptr`` to device pointer ``dst_ptr`` (both
+    16-byte aligned) with ``blocks`` blocks of 256 lanes, complete on return.
+    ``variant`` -1 is the one the probe measures with; a number outside
+    ``SWEEP_UNROLL`` runs variant 0.  Runs on the null stream.  A misaligned
+    pointer or ``blocks < 1`` raises ``GpuLibError`` and launches nothing."""
+    lib = load()
+    _check(
+        lib,
+        lib.csp_hbm_sweep_dev(
+            int(variant), ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), n4, int(blocks)
+        ),
+        "csp_hbm_sweep_dev",
+    )
 
 
 PACK_ALIGN = 16  # every packed segment starts on a multiple of this

@@ -29,7 +29,13 @@
 //                       in the same pass (a cached argument's private copy),
 //   * csp_pack_dev    — one launch gathers many small device buffers into a
 //                       contiguous zero-padded arena, so a result of hundreds
-//                       of small tensors leaves as one streamed frame.
+//                       of small tensors leaves as one streamed frame,
+//   * csp_hbm_sweep_dev
+//                     — one launch of the probe's HBM sweep kernel on the
+//                       caller's buffers (tests: what the sweep copies),
+//   * csp_checksum_grid_cap / csp_copy_checksum_grid_cap
+//                     — tools only: the grid caps of the two checksum
+//                       kernels, so tests reach every loop on tiny data.
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -155,6 +161,32 @@ static sweep_fn sweep_variant(int variant) {
 static int g_sweep_variant = 2;
 
 extern "C" void csp_set_sweep_variant(int v) { g_sweep_variant = v; }
+
+// One launch of the sweep kernel on the caller's buffers: n4 float4 from src
+// to dst (both 16-byte aligned device pointers), `blocks` blocks of 256, on
+// the null stream like run_hbm_sweep, synchronised before returning.  variant
+// < 0 takes g_sweep_variant, an unknown one falls back to variant 0, both
+// through sweep_variant() like the probe: tests check here what the kernel
+// behind hbm_bw_gbps copies.  A misaligned pointer or blocks < 1 return -1
+// with a message and launch nothing.
+extern "C" int csp_hbm_sweep_dev(int variant, const void* src, void* dst, size_t n4,
+                                 int blocks) {
+    if (reinterpret_cast<uintptr_t>(src) % 16 != 0 || reinterpret_cast<uintptr_t>(dst) % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_hbm_sweep_dev: src %p and dst %p must be 16-byte aligned", src, dst);
+        return -1;
+    }
+    if (blocks < 1) {
+        snprintf(g_err, sizeof(g_err), "csp_hbm_sweep_dev: blocks %d is less than 1", blocks);
+        return -1;
+    }
+    sweep_fn kern = sweep_variant(variant < 0 ? g_sweep_variant : variant);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, static_cast<const float4*>(src),
+                       static_cast<float4*>(dst), n4);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
+    return 0;
+}
 
 // ---------------------------------------------------------------------------
 // Device / measurement helpers
@@ -795,6 +827,18 @@ __global__ __launch_bounds__(256) void csp_checksum_kernel(
 
 static std::mutex g_checksum_mu;
 
+static const size_t kChecksumGridCapDefault = 1024;
+static size_t g_checksum_grid_cap = kChecksumGridCapDefault;
+
+// Tools only: the grid cap of the next csp_checksum_dev calls (0 restores
+// the default).  Returns the cap in effect.  With a cap of 1, 2 or 3 blocks
+// a few KiB reach the unrolled loop, the single-vector loop and the hand-off
+// between them.
+extern "C" size_t csp_checksum_grid_cap(size_t cap) {
+    g_checksum_grid_cap = cap ? std::min(cap, size_t(65536)) : kChecksumGridCapDefault;
+    return g_checksum_grid_cap;
+}
+
 // Checksum of nbytes at device pointer dev (16-byte aligned) into out[2].
 // Runs on copy_stream(), so it is ordered after the copies that
 // csp_h2d_stream_fd issued, and synchronises that stream before returning.
@@ -822,7 +866,7 @@ extern "C" int csp_checksum_dev(const void* dev, size_t nbytes, uint64_t out[2])
     const unsigned int tail_bytes = (unsigned int)(nbytes % 16);
     size_t blocks = (n16 + 255) / 256;
     if (blocks < 1) blocks = 1;  // tail only
-    if (blocks > 1024) blocks = 1024;
+    if (blocks > g_checksum_grid_cap) blocks = g_checksum_grid_cap;
     hipStream_t s = copy_stream();
     HIP_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(csp_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0, s,

@@ -21,7 +21,8 @@ pytestmark = pytest.mark.gpu
 CHUNK = 64 * 1024  # tiny, so the two-chunk ring wraps on tiny data
 SIZES = [0, 1, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 17, 3 * CHUNK]
 # the last one is more than one pass of a 1024 x 256-lane grid of 16-byte
-# loads (4 MiB), so the grid-stride loop takes a second trip
+# loads (4 MiB), so the single-vector loop takes a second trip; the 4-way
+# unrolled loop starts at 12 MiB and is covered by test_gpu_checksum_edges
 SUM_SIZES = [0, 1, 3, 4, 15, 16, 17, CHUNK - 1, 256 * 16 * 3 + 5, (4 << 20) + 4096 + 3]
 GUARD = 64
 MARKER = b"\x5a"
