@@ -60,7 +60,7 @@ class SSHClusterExecutor:
     unchanged (``persistent_workers``, ``device_tensor_args``,
     ``pack_tensor_results``, ``pack_results_min_bytes``,
     ``cache_tensor_args``, ``arg_cache_bytes``, ``arg_cache_min_bytes``,
-    ...), so the executor's own validation applies per node.  The argument
+    ``pack_tensor_args``, ``pack_args_min_bytes``, ...), so the executor's own validation applies per node.  The argument
     cache is per worker: an electron that lands on another node, or another
     GPU slot, stores its tensors there first.
     """

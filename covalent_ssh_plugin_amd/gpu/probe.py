@@ -13,9 +13,13 @@ gfx950 only) provides:
 * ``csp_checksum_dev`` — the argument checksum over bytes in HBM,
 * ``csp_pack_dev`` — many small device buffers gathered into one contiguous
   zero-padded arena by one kernel launch (``pack_tensor_results``),
+* ``csp_unpack_checksum_dev`` — such an arena scattered into private
+  per-tensor buffers and checksummed by one kernel launch
+  (``pack_tensor_args``),
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
-  ``csp_copy_checksum_grid_cap`` (tools and tests only).
+  ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
+  and tests only).
 
 On a GPU box these bindings FAIL LOUDLY if the extension is missing or
 broken — there is no eager/CPU fallback for the device path.
@@ -138,6 +142,19 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_pack_tile_bytes.restype = ctypes.c_size_t
     lib.csp_pack_tile_bytes.argtypes = []
+    lib.csp_unpack_checksum_dev.restype = ctypes.c_int
+    lib.csp_unpack_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_unpack_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_unpack_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -363,6 +380,44 @@ def pack_device(segments, arena_ptr: int, arena_bytes: int) -> dict:
         "csp_pack_dev",
     )
     return {"kernel_ms": kernel_ms.value}
+
+
+def unpack_checksum_device(arena_ptr: int, arena_bytes: int, segments) -> dict:
+    """Scatter the 16-byte aligned device arena at ``arena_ptr`` into
+    ``segments``, a sequence of ``(dst_ptr, src_off, nbytes)`` with 16-byte
+    aligned device pointers, and checksum the whole arena in the same kernel
+    launch (``pack_tensor_args``).  The offsets must follow
+    :func:`pack_layout` and ``arena_bytes`` must be its total; a violation, a
+    misaligned pointer or a destination that overlaps the arena raises
+    ``GpuLibError`` and launches nothing.  Overlap between destinations is
+    the caller's responsibility.  Exactly ``nbytes`` bytes are written at
+    each ``dst_ptr`` (0 is allowed for a zero-byte segment) and the arena is
+    only read.  Returns ``{"sum": (s0, s1), "kernel_ms": ...}``: the sum is
+    :func:`checksum_device` of the arena, padding included, and the time is
+    the kernel alone.  Runs on the library's copy stream; work on the buffers
+    on another stream must be complete (``torch.cuda.synchronize()``) first."""
+    lib = load()
+    n = len(segments)
+    dst = (ctypes.c_void_p * n)(*[int(s[0]) or None for s in segments])
+    off = (ctypes.c_uint64 * n)(*[int(s[1]) for s in segments])
+    size = (ctypes.c_uint64 * n)(*[int(s[2]) for s in segments])
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_unpack_checksum_dev(
+            ctypes.c_void_p(arena_ptr), arena_bytes, dst, off, size, n, out,
+            ctypes.byref(kernel_ms),
+        ),
+        "csp_unpack_checksum_dev",
+    )
+    return {"sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
+
+
+def unpack_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`unpack_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_unpack_checksum_grid_cap(int(cap)))
 
 
 def staged_d2h_bytes(data_ptr: int, nbytes: int) -> bytes:

@@ -30,12 +30,19 @@
 //   * csp_pack_dev    — one launch gathers many small device buffers into a
 //                       contiguous zero-padded arena, so a result of hundreds
 //                       of small tensors leaves as one streamed frame,
+//   * csp_unpack_checksum_dev
+//                     — the mirror for arguments: one launch scatters an
+//                       arena of many small tensor arguments into private
+//                       per-tensor buffers and yields the arena's checksum in
+//                       the same pass,
 //   * csp_hbm_sweep_dev
 //                     — one launch of the probe's HBM sweep kernel on the
 //                       caller's buffers (tests: what the sweep copies),
-//   * csp_checksum_grid_cap / csp_copy_checksum_grid_cap
-//                     — tools only: the grid caps of the two checksum
-//                       kernels, so tests reach every loop on tiny data.
+//   * csp_checksum_grid_cap / csp_copy_checksum_grid_cap /
+//     csp_unpack_checksum_grid_cap
+//                     — tools only: the grid caps of the checksum, copy and
+//                       unpack kernels, so tests reach every loop on tiny
+//                       data.
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -1286,6 +1293,324 @@ extern "C" int csp_pack_dev(const void* const* src, const uint64_t* dst_off,
         *kernel_ms = ms;
     }
 #undef PACK_TRY
+    return done(0);
+}
+
+// ---------------------------------------------------------------------------
+// Argument unpacking: one arena scattered into many private buffers, verified
+// ---------------------------------------------------------------------------
+//
+// The argument-direction mirror of csp_pack_dev.  The small tensor arguments
+// of one electron arrive as ONE frame that lands in HBM as one arena (the
+// pack layout); this kernel scatters the arena into the electron's private
+// per-tensor allocations and computes csp_checksum_dev's (s0, s1) of the
+// whole arena in the same pass.  Verification has to read every arena byte
+// anyway, so the scatter costs only the writes.
+//
+// Layout (the pack layout read backwards, checked before anything is
+// launched): segment k is nbytes[k] bytes at arena + src_off[k] and goes to
+// dst[k]; src_off[0] == 0, src_off[k+1] == src_off[k] + round_up(nbytes[k],
+// 16), arena_bytes is the sum of the rounded sizes, arena and every dst are
+// 16-byte aligned.  Every 16-byte arena vector belongs to exactly one
+// segment and is loaded and summed exactly once, padding included and summed
+// as it is (not assumed zero), with word weights from the arena-global word
+// index src_off[k]/4 + i: the result is csp_checksum_dev(arena, arena_bytes)
+// whatever the tiling, because integer sums are exact in any order.
+//
+//   - the pack kernel's decomposition: tiles of kPackTileBytes of one
+//     segment, the prefix of tile counts built on the host, a binary search
+//     per tile that depends on the tile index only (wave-uniform); each block
+//     loops over tiles blockIdx.x, +gridDim.x, ... and carries the checksum
+//     kernel's per-lane u64 s0/t accumulators across all of them, then wave
+//     shuffles, LDS and one atomicAdd pair per block;
+//   - arena loads are aligned plain 16-byte loads (a cached master is read
+//     again by the next hit, so it may stay in the caches); stores of vectors
+//     wholly inside a segment are aligned nontemporal 16-byte stores;
+//   - the last vector of a segment with nbytes % 16 != 0 is loaded and summed
+//     whole, but only its nbytes % 16 data bytes are stored: dst is 16-byte
+//     aligned, so they go out as naturally aligned 8/4/2/1-byte stores picked
+//     by the bits of the remainder.  No byte at or after dst[k] + nbytes[k]
+//     is written, and no arena byte is written at all;
+//   - at most 1024 blocks, the checksum kernels' cap: measured against the
+//     pack kernel's 2048 it was faster on the 200-tensor mix and level on
+//     the other two layouts (0.0958 against 0.1021 ms on 295 MB, 0.0948 against
+//     0.0953 ms on 66 x 4 MiB, 0.0116 ms both on 200 x 4 KiB;
+//     profiles/packed_args.md).
+struct UnpackSeg {
+    unsigned char* dst;
+    unsigned long long src_off;
+    unsigned long long nbytes;
+    unsigned long long tile_begin;  // tiles owned by the segments before this one
+};
+
+typedef CSP_GLOBAL unsigned char* unpack_dst_t;
+
+// the first `r` (1..15) bytes of v to the 16-byte aligned p, nothing after
+__device__ __forceinline__ void unpack_store_tail(unpack_dst_t p, u32x4 v, unsigned int r) {
+    unsigned int pos = 0;
+    if (r & 8u) {
+        *reinterpret_cast<CSP_GLOBAL unsigned long long*>(p) =
+            (unsigned long long)v[0] | ((unsigned long long)v[1] << 32);
+        pos = 8;
+    }
+    if (r & 4u) {
+        // pos is 0 or 8: word 0 or word 2
+        *reinterpret_cast<CSP_GLOBAL unsigned int*>(p + pos) = pos ? v[2] : v[0];
+        pos += 4;
+    }
+    // the word that holds the remaining 0..3 bytes
+    const unsigned int w = pos >= 8 ? (pos >= 12 ? v[3] : v[2]) : (pos >= 4 ? v[1] : v[0]);
+    if (r & 2u) {
+        *reinterpret_cast<CSP_GLOBAL unsigned short*>(p + pos) = (unsigned short)(w & 0xffffu);
+        pos += 2;
+    }
+    if (r & 1u) p[pos] = (unsigned char)((w >> (8 * (pos & 3u))) & 0xffu);
+}
+
+__global__ __launch_bounds__(256) void csp_unpack_checksum_kernel(
+    const UnpackSeg* __restrict__ segs, unsigned int nseg, size_t total_tiles,
+    const unsigned char* __restrict__ arena, unsigned long long* __restrict__ out) {
+    unsigned long long s0 = 0, t = 0;
+    for (size_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+        // last segment whose first tile is <= tile (tile_begin is strictly
+        // increasing: the host leaves zero-byte segments out of the table)
+        unsigned int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].tile_begin <= tile) lo = mid; else hi = mid;
+        }
+        const UnpackSeg s = segs[lo];
+        const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(arena + s.src_off);
+        const unpack_dst_t dst = (unpack_dst_t)s.dst;
+        const size_t nfull = s.nbytes / 16;  // vectors wholly inside the segment
+        const unsigned int tail = (unsigned int)(s.nbytes % 16);
+        const size_t nvec = nfull + (tail ? 1 : 0);  // vectors the segment owns
+        const size_t v0 = (tile - s.tile_begin) * kPackTileVecs + threadIdx.x;
+        // arena-global index of the segment's first word, modulo 2^32 like
+        // csp_checksum_kernel's (unsigned int)(i * 4)
+        const unsigned int word_base = (unsigned int)(s.src_off / 4);
+        if ((tile - s.tile_begin + 1) * kPackTileVecs <= nfull) {
+            // interior tile: every lane has four whole vectors
+            u32x4 v[kPackUnroll];
+#pragma unroll
+            for (int u = 0; u < kPackUnroll; ++u) v[u] = src[v0 + u * 256];
+#pragma unroll
+            for (int u = 0; u < kPackUnroll; ++u) {
+                const size_t vi = v0 + u * 256;
+                __builtin_nontemporal_store(
+                    v[u], reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+                checksum_add(s0, t, v[u], word_base + (unsigned int)(vi * 4));
+            }
+            continue;
+        }
+#pragma unroll
+        for (int u = 0; u < kPackUnroll; ++u) {
+            const size_t vi = v0 + u * 256;
+            if (vi >= nvec) continue;
+            const u32x4 v = src[vi];  // padding included: all 16 bytes are arena
+            checksum_add(s0, t, v, word_base + (unsigned int)(vi * 4));
+            if (vi < nfull)
+                __builtin_nontemporal_store(
+                    v, reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+            else
+                unpack_store_tail(dst + vi * 16, v, tail);
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+static const size_t kUnpackGridCapDefault = 1024;
+static size_t g_unpack_grid_cap = kUnpackGridCapDefault;
+
+// Tools only: the grid cap of the next csp_unpack_checksum_dev calls
+// (0 restores the default).  Returns the cap in effect.  With a cap of 1, 2
+// or 3 blocks a few dozen tiles make every block loop over several tiles.
+extern "C" size_t csp_unpack_checksum_grid_cap(size_t cap) {
+    g_unpack_grid_cap = cap ? std::min(cap, size_t(65536)) : kUnpackGridCapDefault;
+    return g_unpack_grid_cap;
+}
+
+// Scatter the arena's nseg segments to dst[k] (layout rule above) and put
+// csp_checksum_dev(arena, arena_bytes) into out[2].  Returns -1 with a
+// message and launches nothing for: a misaligned arena, a non-null dst that
+// is not 16-byte aligned, a nonzero segment with a null dst, a null arena
+// for a nonzero arena_bytes, a layout violation, an arena_bytes that is not
+// the layout's total, an overflow, nseg >= 2^31, or a destination range
+// [dst[k], dst[k] + nbytes[k]) that overlaps the arena.  Overlap BETWEEN
+// destinations is not checked: it is the caller's responsibility, and two
+// overlapping destinations end with unspecified bytes where they overlap.
+// Zero-byte segments own no tile and their dst may be null.  arena_bytes == 0
+// gives out = (0, 0).  Runs on copy_stream(), so it is ordered after the
+// copies csp_h2d_stream_fd issued, and synchronises that stream before
+// returning; destinations in use on another stream must be complete first.
+// kernel_ms (optional): the kernel alone, from events around the launch.
+extern "C" int csp_unpack_checksum_dev(const void* arena, size_t arena_bytes,
+                                       void* const* dst, const uint64_t* src_off,
+                                       const uint64_t* nbytes, size_t nseg,
+                                       uint64_t out[2], double* kernel_ms) {
+    out[0] = out[1] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(arena);
+    if (a % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_unpack_checksum_dev: arena pointer %p is not 16-byte aligned", arena);
+        return -1;
+    }
+    if (nseg >= (size_t(1) << 31)) {
+        snprintf(g_err, sizeof(g_err), "csp_unpack_checksum_dev: %zu segments are too many",
+                 nseg);
+        return -1;
+    }
+    if (a + arena_bytes < a) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_unpack_checksum_dev: %zu bytes at arena %p overflow", arena_bytes, arena);
+        return -1;
+    }
+    std::vector<UnpackSeg> table;
+    table.reserve(nseg);
+    uint64_t expect = 0, tiles = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        if (src_off[k] != expect) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_unpack_checksum_dev: src_off[%zu] is %llu, the layout rule gives %llu",
+                     k, (unsigned long long)src_off[k], (unsigned long long)expect);
+            return -1;
+        }
+        const uint64_t rounded = (nbytes[k] + 15) & ~uint64_t(15);
+        if (rounded < nbytes[k] || expect + rounded < expect) {
+            snprintf(g_err, sizeof(g_err), "csp_unpack_checksum_dev: segment %zu overflows", k);
+            return -1;
+        }
+        expect += rounded;
+        const uintptr_t d = reinterpret_cast<uintptr_t>(dst[k]);
+        if (d % 16 != 0) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_unpack_checksum_dev: dst[%zu] %p is not 16-byte aligned", k, dst[k]);
+            return -1;
+        }
+        if (nbytes[k] == 0) continue;  // owns no tile
+        if (d == 0) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_unpack_checksum_dev: segment %zu has %llu bytes and a null dst", k,
+                     (unsigned long long)nbytes[k]);
+            return -1;
+        }
+        if (d + nbytes[k] < d) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_unpack_checksum_dev: dst[%zu] %p with %llu bytes overflows", k, dst[k],
+                     (unsigned long long)nbytes[k]);
+            return -1;
+        }
+        table.push_back({static_cast<unsigned char*>(dst[k]), src_off[k], nbytes[k], tiles});
+        tiles += (rounded + kPackTileBytes - 1) / kPackTileBytes;
+    }
+    if (expect != (uint64_t)arena_bytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_unpack_checksum_dev: arena_bytes is %zu, the segments need %llu",
+                 arena_bytes, (unsigned long long)expect);
+        return -1;
+    }
+    if (arena_bytes == 0) return 0;
+    if (arena == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_unpack_checksum_dev: null arena for %zu bytes",
+                 arena_bytes);
+        return -1;
+    }
+    for (size_t k = 0; k < table.size(); ++k) {
+        const uintptr_t d = reinterpret_cast<uintptr_t>(table[k].dst);
+        if (d < a + arena_bytes && a < d + table[k].nbytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_unpack_checksum_dev: %llu bytes at dst %p overlap the arena at %p",
+                     (unsigned long long)table[k].nbytes, (void*)table[k].dst, arena);
+            return -1;
+        }
+    }
+
+    // one accumulator pair and one grow-only table per process, one call at
+    // a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static UnpackSeg* dev_table = nullptr;
+    static size_t dev_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_device != device) {
+        if (acc) (void)hipFree(acc);
+        if (dev_table) (void)hipFree(dev_table);
+        acc = nullptr;
+        dev_table = nullptr;
+        dev_cap = 0;
+        dev_device = device;
+    }
+    if (acc == nullptr) HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+    if (dev_table == nullptr || dev_cap < table.size()) {
+        if (dev_table) (void)hipFree(dev_table);
+        dev_table = nullptr;
+        dev_cap = 0;
+        size_t cap = 1024;
+        while (cap < table.size()) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_table, cap * sizeof(UnpackSeg)));
+        dev_cap = cap;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define UNPACK_TRY(expr)                                           \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    // `table` outlives the copy: the stream is synchronised below
+    UNPACK_TRY(hipMemcpyAsync(dev_table, table.data(), table.size() * sizeof(UnpackSeg),
+                              hipMemcpyHostToDevice, s));
+    UNPACK_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t blocks = tiles < g_unpack_grid_cap ? (size_t)tiles : g_unpack_grid_cap;
+    if (t0) UNPACK_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_unpack_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       dev_table, (unsigned int)table.size(), (size_t)tiles,
+                       static_cast<const unsigned char*>(arena), acc);
+    UNPACK_TRY(hipGetLastError());
+    if (t1) UNPACK_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    UNPACK_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    UNPACK_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        UNPACK_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef UNPACK_TRY
+    out[0] = host[0];
+    out[1] = host[1];
     return done(0);
 }
 

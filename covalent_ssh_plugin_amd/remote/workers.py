@@ -27,7 +27,7 @@ import cloudpickle
 
 from ..compat import app_log
 from ..transport import native_io
-from ..transport.channel import Channel, ChannelClosed
+from ..transport.channel import Channel, ChannelClosed, FrameParts
 
 WorkerKey = Tuple[object, ...]
 
@@ -220,9 +220,143 @@ def tensor_content_key(tensor, view) -> str:
     return key
 
 
+PACKED_MARKER = "__csp_packed_tensor_v1__"
+PACKED_KEY_DOMAIN = b"csp-packed-v1"
+PACK_ALIGN = 16  # csp_pack_dev's layout rule: every segment starts on a multiple
+# A packed argument arena never exceeds this: every arena word index then
+# stays far below 2^32, where the checksum's weight wraps, so
+# compose_packed_checksum is exact.  A condition, not a measurement.
+PACK_ARGS_MAX_BYTES = 4 << 30
+
+
+def compose_packed_checksum(sums, offsets):
+    """``native_io.checksum`` of a packed arena, from the checksums of its
+    segments alone, so the dispatcher never materialises the arena.
+
+    Segment ``k`` is tensor ``k``'s bytes at ``offsets[k]``, a multiple of
+    16, followed by zeros up to the next multiple of 16.  Alone, its
+    little-endian words ``w_i`` give ``s0_k = sum w_i`` and
+    ``s1_k = sum w_i * (i + 1)``; a last word cut short is zero-extended
+    there exactly as the arena's padding extends it.  In the arena word ``i``
+    of segment ``k`` has the global index ``offsets[k] / 4 + i``, hence the
+    weight ``offsets[k] / 4 + i + 1``, and contributes
+    ``w_i * (i + 1) + (offsets[k] / 4) * w_i``.  Padding words are zero and
+    contribute nothing.  Summed over the segment and then over all segments,
+    modulo 2^64:
+
+        s0 = sum s0_k
+        s1 = sum (s1_k + (offsets[k] / 4) * s0_k)
+
+    This needs every word index below 2^32 (the weight is taken modulo 2^32
+    before the product): :data:`PACK_ARGS_MAX_BYTES` keeps it below 2^30."""
+    mask = (1 << 64) - 1
+    s0 = s1 = 0
+    for (c0, c1), off in zip(sums, offsets):
+        s0 += c0
+        s1 += c1 + (off // 4) * c0
+    return s0 & mask, s1 & mask
+
+
+def packed_content_key(segment_keys) -> str:
+    """The cache identity of a packed arena: blake2b over a domain tag and
+    each segment's ``(content key, byte count)`` in order.  A key of keys:
+    the per-tensor memo of :func:`tensor_content_key` makes a repeated set of
+    the same tensor objects free to key."""
+    outer = hashlib.blake2b(PACKED_KEY_DOMAIN, digest_size=16)
+    for key, nbytes in segment_keys:
+        outer.update(bytes.fromhex(key))
+        outer.update(struct.pack("<Q", nbytes))
+    return outer.hexdigest()
+
+
+def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
+                     buffers, buffer_meta):
+    """The ``pack_tensor_args`` half of :func:`extract_arg_buffers`: emit the
+    packed entry when the rule in its docstring holds.  Returns
+    ``{id(tensor): marker}``, empty when nothing is packed.  Only called with
+    the option on, so the per-tensor path pays nothing for it."""
+    import ctypes
+
+    import torch
+
+    packed_markers = {}
+    found = {}
+
+    def nbytes_of(t):
+        return t.numel() * t.element_size()
+
+    def collect(obj):
+        if isinstance(obj, torch.Tensor):
+            n = nbytes_of(obj)
+            if (
+                not obj.is_cuda
+                and n < threshold
+                and (cache_min_bytes is None or n < cache_min_bytes)
+            ):
+                found.setdefault(id(obj), obj)
+        elif isinstance(obj, dict):
+            for v in obj.values():
+                collect(v)
+        elif isinstance(obj, (tuple, list)):
+            for v in obj:
+                collect(v)
+
+    collect(list(args))
+    collect(dict(kwargs))
+    tensors = list(found.values())
+    if len(tensors) < 2:
+        return packed_markers
+    sizes = [nbytes_of(t) for t in tensors]
+    offsets = []
+    total = 0
+    for n in sizes:
+        offsets.append(total)
+        total += (n + PACK_ALIGN - 1) // PACK_ALIGN * PACK_ALIGN
+    if total < pack_min_bytes or total == 0 or total > PACK_ARGS_MAX_BYTES:
+        return packed_markers
+    srcs = [t.contiguous() for t in tensors]
+    parts = []
+    views = []
+    for src_t, n in zip(srcs, sizes):
+        view = (ctypes.c_char * n).from_address(src_t.data_ptr()) if n else b""
+        views.append(view)
+        parts.append(view)
+        if n % PACK_ALIGN:
+            parts.append(bytes(PACK_ALIGN - n % PACK_ALIGN))
+    info = {
+        "device": True,
+        "packed": [
+            {"dtype": str(s.dtype).replace("torch.", ""), "shape": list(s.shape),
+             "offset": off, "nbytes": n}
+            for s, off, n in zip(srcs, offsets, sizes)
+        ],
+        "nbytes": total,
+    }
+    # looked up at call time: None when libcsp_io.so is not loaded
+    sums = [native_io.checksum(v) if n else (0, 0) for v, n in zip(views, sizes)]
+    if all(s is not None for s in sums):
+        s0, s1 = compose_packed_checksum(sums, offsets)
+        info["sum"] = [int(s0), int(s1)]
+        if cache_min_bytes is not None and total >= max(1, cache_min_bytes):
+            info["cache"] = {
+                "key": packed_content_key(
+                    (tensor_content_key(t, v), n)
+                    for t, v, n in zip(tensors, views, sizes)
+                )
+            }
+    # the source tensors stay alive until the frame is drained
+    buffers.append((FrameParts(parts), srcs))
+    buffer_meta.append(info)
+    index = len(buffers) - 1
+    for j, t in enumerate(tensors):
+        packed_markers[id(t)] = (PACKED_MARKER, index, j)
+    return packed_markers
+
+
 def extract_arg_buffers(
     args, kwargs, threshold: int, to_device: bool = False,
     cache_min_bytes: Optional[int] = None,
+    pack_min_bytes: Optional[int] = None,
 ):
     """Pull large contiguous CPU torch tensors out of (args, kwargs) and
     replace them with out-of-band buffer markers (the request-direction
@@ -244,7 +378,24 @@ def extract_arg_buffers(
     marked ``"device": True`` (the worker lands it in HBM) and, when the
     native I/O library is loaded, carries ``"sum": [s0, s1]``, the checksum
     of the contiguous bytes that will be sent (the worker recomputes it on
-    the GPU and compares)."""
+    the GPU and compares).
+
+    ``pack_min_bytes`` (the executor's ``pack_tensor_args``; ``None`` is off)
+    with ``to_device``: the CPU tensors below ``threshold`` (and, with the
+    cache on, below ``cache_min_bytes``: a tensor at or above it keeps its
+    own key and master) travel as ONE frame when at least two distinct
+    tensor objects qualify and their arena (each tensor at the next multiple
+    of 16 bytes, ``csp_pack_dev``'s layout) is at least ``pack_min_bytes``
+    and at most :data:`PACK_ARGS_MAX_BYTES`.  The entry is ``{"device": True,
+    "packed": [{dtype, shape, offset, nbytes}, ...], "nbytes": total,
+    "sum": [s0, s1]}``, its buffer a :class:`FrameParts` over the tensors'
+    own memory and the zero padding (no host arena), its checksum composed by
+    :func:`compose_packed_checksum`, and each tensor becomes
+    ``("__csp_packed_tensor_v1__", i, j)``: one tensor object met twice is
+    one segment and one marker.  With the cache on and
+    ``total >= cache_min_bytes`` the entry carries ``"cache": {"key"}`` from
+    :func:`packed_content_key`.  Otherwise every tensor takes the per-tensor
+    path, exactly as without the option."""
     import sys
 
     if "torch" not in sys.modules:
@@ -255,8 +406,15 @@ def extract_arg_buffers(
 
     buffer_meta = []
     buffers = []
+    packed_markers = None  # id(tensor) -> marker, with pack_tensor_args
+    if to_device and pack_min_bytes is not None:
+        packed_markers = _pack_small_args(
+            args, kwargs, threshold, cache_min_bytes, pack_min_bytes, buffers, buffer_meta
+        )
 
     def extract(t):
+        if packed_markers and id(t) in packed_markers:
+            return packed_markers[id(t)]
         src_t = t.contiguous()
         nbytes = src_t.numel() * src_t.element_size()
         view = (ctypes.c_char * nbytes).from_address(src_t.data_ptr())
@@ -397,6 +555,11 @@ def _reconstruct(result, buffer_meta, buffers):
     return walk(result)
 
 
+def _view_nbytes(view) -> int:
+    """Bytes of one argument frame: a buffer, or the parts of a packed one."""
+    return view.nbytes if isinstance(view, FrameParts) else memoryview(view).nbytes
+
+
 class _ArgCacheSend:
     """The ``cache_tensor_args`` side of one :func:`run_task`: which cached
     entries travel as a reference, decided while the request is being sent,
@@ -448,7 +611,7 @@ class _ArgCacheSend:
                 if ref and key in held:
                     stats["arg_cache_hits"] = stats.get("arg_cache_hits", 0) + 1
                     stats["arg_cache_bytes_saved"] = (
-                        stats.get("arg_cache_bytes_saved", 0) + memoryview(view).nbytes
+                        stats.get("arg_cache_bytes_saved", 0) + _view_nbytes(view)
                     )
             stats["arg_cache_misses"] = stats.get("arg_cache_misses", 0) + len(missed)
         return bool(missed)

@@ -23,6 +23,48 @@ class ChannelClosed(ConnectionError):
     """The remote worker process went away (EOF on its stdout)."""
 
 
+class FrameParts:
+    """The payload of ONE frame given as an ordered list of buffer-protocol
+    parts (``pack_tensor_args``: the tensors of a packed argument arena and
+    the zero padding between them, never copied into a second host buffer).
+    ``nbytes`` is the total.  :meth:`Channel.send_frame` writes the 8-byte
+    length of the total and then the parts in order."""
+
+    # parts below SMALL are gathered into one write of up to about GATHER
+    SMALL = 64 * 1024
+    GATHER = 1 << 20
+
+    def __init__(self, parts):
+        self.parts = [memoryview(p).cast("B") for p in parts]
+        self.nbytes = sum(p.nbytes for p in self.parts)
+
+    def writes(self):
+        """The payload as a sequence of buffers to write: runs of parts below
+        ``SMALL`` coalesced into one ``bytes`` of at most about ``GATHER``,
+        larger parts as they are (no copy)."""
+        run = []
+        size = 0
+        for part in self.parts:
+            if part.nbytes == 0:
+                continue
+            if part.nbytes >= self.SMALL:
+                if run:
+                    yield b"".join(run)
+                    run, size = [], 0
+                yield part
+                continue
+            run.append(part)
+            size += part.nbytes
+            if size >= self.GATHER:
+                yield b"".join(run)
+                run, size = [], 0
+        if run:
+            yield b"".join(run)
+
+    def tobytes(self) -> bytes:
+        return b"".join(self.parts)
+
+
 class _PipeFrameReader(asyncio.Protocol):
     """Read side of a channel: the project's own protocol on the worker's
     stdout pipe (``loop.connect_read_pipe``) in place of a StreamReader.
@@ -240,7 +282,14 @@ class Channel:
         views of pinned/tensor memory go out without copies)."""
         if not self.alive:
             raise ChannelClosed(f"{self._label}: process exited")
-        view = memoryview(payload).cast("B")
+        try:
+            view = memoryview(payload).cast("B")
+        except TypeError:
+            # not a buffer: a FrameParts (off the hot path of plain frames)
+            if not isinstance(payload, FrameParts):
+                raise
+            await self._send_parts(payload)
+            return
         if view.nbytes <= 64 * 1024:
             # hot path (small control/request frames): one buffered write
             # instead of two halves the syscall/transport work per frame
@@ -249,6 +298,17 @@ class Channel:
             # large frames (tensor buffers): never copy
             self._proc.stdin.write(struct.pack(">Q", view.nbytes))
             self._proc.stdin.write(view)
+        await self._proc.stdin.drain()
+
+    async def _send_parts(self, payload: FrameParts) -> None:
+        """One frame from many buffers: the length of the total, then the
+        parts in order, small ones gathered, large ones never copied."""
+        self._proc.stdin.write(struct.pack(">Q", payload.nbytes))
+        for piece in payload.writes():
+            self._proc.stdin.write(piece)
+            if len(piece) >= FrameParts.SMALL:
+                # keep the transport's buffer from holding the whole frame
+                await self._proc.stdin.drain()
         await self._proc.stdin.drain()
 
     async def _recv_large(self, length: int):
