@@ -16,6 +16,9 @@ gfx950 only) provides:
 * ``csp_unpack_checksum_dev`` — such an arena scattered into private
   per-tensor buffers and checksummed by one kernel launch
   (``pack_tensor_args``),
+* ``csp_patch_unpack_checksum_dev`` — the same launch on a held arena, with
+  the changed segments written over it in place from a small delta arena
+  (``patch_tensor_args``),
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
   ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
@@ -147,6 +150,20 @@ def load(path: str = "") -> ctypes.CDLL:
         ctypes.c_void_p,
         ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_patch_unpack_checksum_dev.restype = ctypes.c_int
+    lib.csp_patch_unpack_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_size_t,
@@ -414,9 +431,53 @@ def unpack_checksum_device(arena_ptr: int, arena_bytes: int, segments) -> dict:
     return {"sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
 
 
+PATCH_UNCHANGED = (1 << 64) - 1  # a segment's delta_off when it is not patched
+
+
+def patch_unpack_checksum_device(
+    master_ptr: int, arena_bytes: int, delta_ptr: int, delta_bytes: int, segments
+) -> dict:
+    """:func:`unpack_checksum_device` on a held arena of which some segments
+    changed (``patch_tensor_args``).  ``segments`` is a sequence of
+    ``(dst_ptr, src_off, nbytes, delta_off_or_None)``: a segment with a
+    ``delta_off`` takes its new bytes from the device arena at ``delta_ptr``,
+    where the patched segments, in order, follow :func:`pack_layout` and
+    total ``delta_bytes``.  In one kernel launch the patched segments'
+    16-byte vectors are written over the master in place (their padding as
+    the delta has it), every segment of the patched master is scattered to
+    its ``dst_ptr``, and the master as it is afterwards is checksummed.  The
+    delta is only read, and no master byte outside a patched segment is
+    written.  A layout violation, a misaligned pointer, or an overlap of the
+    delta with the master or a destination raises ``GpuLibError`` and
+    launches nothing.  Returns ``{"sum": (s0, s1), "kernel_ms": ...}``.
+    Shares the grid cap of :func:`unpack_checksum_grid_cap`.  Runs on the
+    library's copy stream; work on the buffers on another stream must be
+    complete (``torch.cuda.synchronize()``) first."""
+    lib = load()
+    n = len(segments)
+    dst = (ctypes.c_void_p * n)(*[int(s[0]) or None for s in segments])
+    off = (ctypes.c_uint64 * n)(*[int(s[1]) for s in segments])
+    size = (ctypes.c_uint64 * n)(*[int(s[2]) for s in segments])
+    delta_off = (ctypes.c_uint64 * n)(
+        *[PATCH_UNCHANGED if s[3] is None else int(s[3]) for s in segments]
+    )
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_patch_unpack_checksum_dev(
+            ctypes.c_void_p(master_ptr), arena_bytes, ctypes.c_void_p(delta_ptr),
+            delta_bytes, dst, off, size, delta_off, n, out, ctypes.byref(kernel_ms),
+        ),
+        "csp_patch_unpack_checksum_dev",
+    )
+    return {"sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
+
+
 def unpack_checksum_grid_cap(cap: int = 0) -> int:
-    """Tools only: set the grid cap of :func:`unpack_checksum_device` (0
-    restores the shipped default).  Returns the cap in effect."""
+    """Tools only: set the grid cap of :func:`unpack_checksum_device` and
+    :func:`patch_unpack_checksum_device` (0 restores the shipped default).
+    Returns the cap in effect."""
     return int(load().csp_unpack_checksum_grid_cap(int(cap)))
 
 

@@ -35,14 +35,20 @@
 //                       arena of many small tensor arguments into private
 //                       per-tensor buffers and yields the arena's checksum in
 //                       the same pass,
+//   * csp_patch_unpack_checksum_dev
+//                     — the same pass over a cached arena of which a few
+//                       segments changed: the changed segments, sent as a
+//                       small delta arena, are written over the held master
+//                       in place while the whole new arena is scattered and
+//                       checksummed,
 //   * csp_hbm_sweep_dev
 //                     — one launch of the probe's HBM sweep kernel on the
 //                       caller's buffers (tests: what the sweep copies),
 //   * csp_checksum_grid_cap / csp_copy_checksum_grid_cap /
 //     csp_unpack_checksum_grid_cap
 //                     — tools only: the grid caps of the checksum, copy and
-//                       unpack kernels, so tests reach every loop on tiny
-//                       data.
+//                       unpack kernels (the patch kernel shares the unpack
+//                       kernel's), so tests reach every loop on tiny data.
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -1609,6 +1615,350 @@ extern "C" int csp_unpack_checksum_dev(const void* arena, size_t arena_bytes,
         *kernel_ms = ms;
     }
 #undef UNPACK_TRY
+    out[0] = host[0];
+    out[1] = host[1];
+    return done(0);
+}
+
+// ---------------------------------------------------------------------------
+// Argument patching: a cached arena updated in place, unpacked and verified
+// ---------------------------------------------------------------------------
+//
+// A cached packed arena (the master) of which only a few segments changed is
+// not sent again: the changed segments arrive as a small delta arena, and this
+// kernel, in the ONE pass that csp_unpack_checksum_dev makes anyway, writes
+// them over the master, scatters the whole new arena into the electron's
+// private buffers and computes csp_checksum_dev's (s0, s1) of the master as it
+// is afterwards.
+//
+// Layout: master, src_off, nbytes, dst and arena_bytes follow the unpack
+// layout rule above.  delta_off[k] == UINT64_MAX: segment k is unchanged.
+// Otherwise its new bytes are at delta + delta_off[k]; the patched segments,
+// in segment order, obey the pack layout inside the delta (the first at 0,
+// each next one at the previous offset plus round_up(nbytes, 16)), and
+// delta_bytes is that total.
+//
+//   - the unpack kernel's decomposition, unchanged: tiles of kPackTileBytes
+//     of one segment, the host-built tile prefix, a binary search per tile
+//     that depends on the tile index only, per-lane u64 s0/t accumulators
+//     carried across a block's tiles, wave shuffles, LDS, one atomicAdd pair
+//     per block, 256-thread blocks, the unpack kernel's grid cap (its 1024 is
+//     taken over, not measured for this kernel);
+//   - the table entry gains the patch source (null: unchanged), so the choice
+//     of source is per tile and wave-uniform;
+//   - an unchanged segment takes exactly the unpack path: plain aligned
+//     16-byte loads from the master, nontemporal stores to dst, the tail as
+//     aligned 8/4/2/1-byte pieces; nothing is written to the master;
+//   - a patched segment loads every 16-byte vector it owns from the delta
+//     (read once: nontemporal), stores it whole to the master with a plain
+//     aligned 16-byte store (the master is re-read by the next hit; the
+//     padding of the last vector goes in as the delta has it), stores it to
+//     dst by the unpack rules and sums it with the master-global word index;
+//   - the delta is never written, no master byte outside a patched segment's
+//     vectors is written, and a patched segment is never read from the
+//     master, so no lane reads what another writes inside the launch.
+struct PatchSeg {
+    unsigned char* dst;
+    const unsigned char* patch;  // the segment's new bytes in the delta, or null
+    unsigned long long src_off;
+    unsigned long long nbytes;
+    unsigned long long tile_begin;  // tiles owned by the segments before this one
+};
+
+__global__ __launch_bounds__(256) void csp_patch_unpack_checksum_kernel(
+    const PatchSeg* __restrict__ segs, unsigned int nseg, size_t total_tiles,
+    unsigned char* master, unsigned long long* __restrict__ out) {
+    unsigned long long s0 = 0, t = 0;
+    for (size_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+        // last segment whose first tile is <= tile (tile_begin is strictly
+        // increasing: the host leaves zero-byte segments out of the table)
+        unsigned int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].tile_begin <= tile) lo = mid; else hi = mid;
+        }
+        const PatchSeg s = segs[lo];
+        CSP_GLOBAL u32x4* mst = reinterpret_cast<CSP_GLOBAL u32x4*>(
+            (CSP_GLOBAL unsigned char*)(master + s.src_off));
+        const CSP_GLOBAL u32x4* patch = reinterpret_cast<const CSP_GLOBAL u32x4*>(
+            (const CSP_GLOBAL unsigned char*)s.patch);
+        const bool patched = s.patch != nullptr;  // per tile: wave-uniform
+        const unpack_dst_t dst = (unpack_dst_t)s.dst;
+        const size_t nfull = s.nbytes / 16;  // vectors wholly inside the segment
+        const unsigned int tail = (unsigned int)(s.nbytes % 16);
+        const size_t nvec = nfull + (tail ? 1 : 0);  // vectors the segment owns
+        const size_t v0 = (tile - s.tile_begin) * kPackTileVecs + threadIdx.x;
+        // master-global index of the segment's first word, modulo 2^32 like
+        // csp_checksum_kernel's (unsigned int)(i * 4)
+        const unsigned int word_base = (unsigned int)(s.src_off / 4);
+        if ((tile - s.tile_begin + 1) * kPackTileVecs <= nfull) {
+            // interior tile: every lane has four whole vectors
+            u32x4 v[kPackUnroll];
+            if (patched) {
+#pragma unroll
+                for (int u = 0; u < kPackUnroll; ++u)
+                    v[u] = __builtin_nontemporal_load(&patch[v0 + u * 256]);
+#pragma unroll
+                for (int u = 0; u < kPackUnroll; ++u) mst[v0 + u * 256] = v[u];
+            } else {
+#pragma unroll
+                for (int u = 0; u < kPackUnroll; ++u) v[u] = mst[v0 + u * 256];
+            }
+#pragma unroll
+            for (int u = 0; u < kPackUnroll; ++u) {
+                const size_t vi = v0 + u * 256;
+                __builtin_nontemporal_store(
+                    v[u], reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+                checksum_add(s0, t, v[u], word_base + (unsigned int)(vi * 4));
+            }
+            continue;
+        }
+#pragma unroll
+        for (int u = 0; u < kPackUnroll; ++u) {
+            const size_t vi = v0 + u * 256;
+            if (vi >= nvec) continue;
+            u32x4 v;  // padding included: all 16 bytes are delta or master
+            if (patched) {
+                v = __builtin_nontemporal_load(&patch[vi]);
+                mst[vi] = v;
+            } else {
+                v = mst[vi];
+            }
+            checksum_add(s0, t, v, word_base + (unsigned int)(vi * 4));
+            if (vi < nfull)
+                __builtin_nontemporal_store(
+                    v, reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+            else
+                unpack_store_tail(dst + vi * 16, v, tail);
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+// Patch the master's segments that have a delta_off (layout rule above) with
+// their bytes from the delta, scatter the nseg segments of the patched master
+// to dst[k], and put csp_checksum_dev(master, arena_bytes) of the master as
+// it is after the call into out[2].  Returns -1 with a message and launches
+// nothing for every refusal of csp_unpack_checksum_dev (master in the place
+// of its arena) and for: a misaligned delta, a null delta for a nonzero
+// delta_bytes, a delta_off that breaks the delta layout rule, a delta_bytes
+// that is not the rule's total, an overflow, or a delta range that overlaps
+// the master or any destination range; ranges that merely touch are accepted.
+// delta_bytes == 0 with every delta_off == UINT64_MAX is an unpack that
+// leaves the master untouched.  Shares the unpack kernel's grid cap
+// (csp_unpack_checksum_grid_cap).  Runs on copy_stream(), so it is ordered
+// after the copies csp_h2d_stream_fd issued, and synchronises that stream
+// before returning; buffers in use on another stream must be complete first.
+// kernel_ms (optional): the kernel alone, from events around the launch.
+extern "C" int csp_patch_unpack_checksum_dev(void* master, size_t arena_bytes,
+                                             const void* delta, size_t delta_bytes,
+                                             void* const* dst, const uint64_t* src_off,
+                                             const uint64_t* nbytes,
+                                             const uint64_t* delta_off, size_t nseg,
+                                             uint64_t out[2], double* kernel_ms) {
+    static const char* const fn = "csp_patch_unpack_checksum_dev";
+    out[0] = out[1] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(master);
+    const uintptr_t p = reinterpret_cast<uintptr_t>(delta);
+    if (a % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: master pointer %p is not 16-byte aligned", fn,
+                 master);
+        return -1;
+    }
+    if (p % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: delta pointer %p is not 16-byte aligned", fn,
+                 delta);
+        return -1;
+    }
+    if (nseg >= (size_t(1) << 31)) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu segments are too many", fn, nseg);
+        return -1;
+    }
+    if (a + arena_bytes < a) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at master %p overflow", fn, arena_bytes,
+                 master);
+        return -1;
+    }
+    if (p + delta_bytes < p) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at delta %p overflow", fn, delta_bytes,
+                 delta);
+        return -1;
+    }
+    std::vector<PatchSeg> table;
+    table.reserve(nseg);
+    uint64_t expect = 0, delta_expect = 0, tiles = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        if (src_off[k] != expect) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: src_off[%zu] is %llu, the layout rule gives %llu", fn, k,
+                     (unsigned long long)src_off[k], (unsigned long long)expect);
+            return -1;
+        }
+        const uint64_t rounded = (nbytes[k] + 15) & ~uint64_t(15);
+        if (rounded < nbytes[k] || expect + rounded < expect) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu overflows", fn, k);
+            return -1;
+        }
+        expect += rounded;
+        const bool patched = delta_off[k] != UINT64_MAX;
+        if (patched) {
+            if (delta_off[k] != delta_expect) {
+                snprintf(g_err, sizeof(g_err),
+                         "%s: delta_off[%zu] is %llu, the delta layout rule gives %llu", fn, k,
+                         (unsigned long long)delta_off[k], (unsigned long long)delta_expect);
+                return -1;
+            }
+            delta_expect += rounded;  // <= expect: cannot overflow
+        }
+        const uintptr_t d = reinterpret_cast<uintptr_t>(dst[k]);
+        if (d % 16 != 0) {
+            snprintf(g_err, sizeof(g_err), "%s: dst[%zu] %p is not 16-byte aligned", fn, k,
+                     dst[k]);
+            return -1;
+        }
+        if (nbytes[k] == 0) continue;  // owns no tile
+        if (d == 0) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu has %llu bytes and a null dst", fn,
+                     k, (unsigned long long)nbytes[k]);
+            return -1;
+        }
+        if (d + nbytes[k] < d) {
+            snprintf(g_err, sizeof(g_err), "%s: dst[%zu] %p with %llu bytes overflows", fn, k,
+                     dst[k], (unsigned long long)nbytes[k]);
+            return -1;
+        }
+        table.push_back({static_cast<unsigned char*>(dst[k]),
+                         patched ? static_cast<const unsigned char*>(delta) + delta_off[k]
+                                 : nullptr,
+                         src_off[k], nbytes[k], tiles});
+        tiles += (rounded + kPackTileBytes - 1) / kPackTileBytes;
+    }
+    if (expect != (uint64_t)arena_bytes) {
+        snprintf(g_err, sizeof(g_err), "%s: arena_bytes is %zu, the segments need %llu", fn,
+                 arena_bytes, (unsigned long long)expect);
+        return -1;
+    }
+    if (delta_expect != (uint64_t)delta_bytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: delta_bytes is %zu, the patched segments need %llu", fn, delta_bytes,
+                 (unsigned long long)delta_expect);
+        return -1;
+    }
+    if (arena_bytes == 0) return 0;
+    if (master == nullptr) {
+        snprintf(g_err, sizeof(g_err), "%s: null master for %zu bytes", fn, arena_bytes);
+        return -1;
+    }
+    if (delta == nullptr && delta_bytes != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: null delta for %zu bytes", fn, delta_bytes);
+        return -1;
+    }
+    if (delta_bytes != 0 && p < a + arena_bytes && a < p + delta_bytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: %zu bytes at delta %p overlap the master at %p", fn, delta_bytes, delta,
+                 master);
+        return -1;
+    }
+    for (size_t k = 0; k < table.size(); ++k) {
+        const uintptr_t d = reinterpret_cast<uintptr_t>(table[k].dst);
+        if (d < a + arena_bytes && a < d + table[k].nbytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: %llu bytes at dst %p overlap the master at %p", fn,
+                     (unsigned long long)table[k].nbytes, (void*)table[k].dst, master);
+            return -1;
+        }
+        if (delta_bytes != 0 && d < p + delta_bytes && p < d + table[k].nbytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: %llu bytes at dst %p overlap the delta at %p", fn,
+                     (unsigned long long)table[k].nbytes, (void*)table[k].dst, delta);
+            return -1;
+        }
+    }
+
+    // one accumulator pair and one grow-only table per process, one call at
+    // a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static PatchSeg* dev_table = nullptr;
+    static size_t dev_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_device != device) {
+        if (acc) (void)hipFree(acc);
+        if (dev_table) (void)hipFree(dev_table);
+        acc = nullptr;
+        dev_table = nullptr;
+        dev_cap = 0;
+        dev_device = device;
+    }
+    if (acc == nullptr) HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+    if (dev_table == nullptr || dev_cap < table.size()) {
+        if (dev_table) (void)hipFree(dev_table);
+        dev_table = nullptr;
+        dev_cap = 0;
+        size_t cap = 1024;
+        while (cap < table.size()) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_table, cap * sizeof(PatchSeg)));
+        dev_cap = cap;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define PATCH_TRY(expr)                                            \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    // `table` outlives the copy: the stream is synchronised below
+    PATCH_TRY(hipMemcpyAsync(dev_table, table.data(), table.size() * sizeof(PatchSeg),
+                             hipMemcpyHostToDevice, s));
+    PATCH_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t blocks = tiles < g_unpack_grid_cap ? (size_t)tiles : g_unpack_grid_cap;
+    if (t0) PATCH_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_patch_unpack_checksum_kernel, dim3((unsigned int)blocks), dim3(256),
+                       0, s, dev_table, (unsigned int)table.size(), (size_t)tiles,
+                       static_cast<unsigned char*>(master), acc);
+    PATCH_TRY(hipGetLastError());
+    if (t1) PATCH_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    PATCH_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    PATCH_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        PATCH_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef PATCH_TRY
     out[0] = host[0];
     out[1] = host[1];
     return done(0);

@@ -46,8 +46,18 @@ Protocol (all frames: 8-byte big-endian length + payload):
              frame lands in HBM as one arena, csp_unpack_checksum_dev
              scatters it into a private tensor per segment and yields the
              arena's checksum in the same pass.  Such an entry may carry
-             "cache" like any other: the arena is then the master.
-  ack     = pickle tuple ("A1", op_id) — written as soon as the request
+             "cache" like any other: the arena is then the master.  With
+             the executor option patch_tensor_args it may instead carry
+             "cache": {"key": NEW, "patch": {"base": BASE, "segments":
+             [j, ...]}} and "patch_nbytes": its ONE frame is then a delta
+             arena of patch_nbytes bytes, the named segments in order in
+             the same layout, and csp_patch_unpack_checksum_dev writes them
+             over the master held under BASE in place, scatters the whole
+             new arena and yields its checksum in one pass; the master is
+             then held under NEW and meta["arg_cache"]["patched"] lists
+             [BASE, NEW].  An absent BASE or a wrong checksum is a miss
+             like a missed "ref", and the master goes.
+  ack    = pickle tuple ("A1", op_id) — written as soon as the request
              (and its arg frames) has been fully received, BEFORE any
              user code runs.  The dispatcher uses it to distinguish
              "worker died before starting the task" (safe to retry on a
@@ -248,6 +258,20 @@ def _load_gpu_lib():
         ctypes.c_void_p,
         ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_patch_unpack_checksum_dev.restype = ctypes.c_int
+    lib.csp_patch_unpack_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_size_t,
@@ -916,6 +940,142 @@ def _packed_args_from_cache(lib, index, info, total, key, stage, report):
     )
 
 
+def _packed_chunk():
+    return min(STREAM_CHUNK, PACKED_ARG_CHUNK) if STREAM_CHUNK > 0 else PACKED_ARG_CHUNK
+
+
+def _patch_packed_args(lib, index, info, total, cache, stage, report):
+    """A ``patch`` packed entry: the frame is a delta arena, the changed
+    segments of the held arena ``base`` in the pack layout.  ONE
+    csp_patch_unpack_checksum_dev call writes them over the master in place,
+    scatters the whole new arena into private tensors and yields its
+    checksum; the master is then held under the new key.  The frame is
+    consumed whatever happens.  An absent base, another byte count, no
+    ``sum`` or another checksum is a miss as in _packed_args_from_cache, and
+    the master goes: after a failed patch in place its bytes are unknown.
+    When the new key is already held the frame is only drained, the base
+    stays, and the tensors come from the arena held under the new key."""
+    import ctypes
+
+    import torch
+
+    new_key = cache["key"]
+    base_key = cache["patch"]["base"]
+    delta_total = int(info["patch_nbytes"])
+    converged = new_key in _arg_cache
+    entry = _arg_cache.get(base_key)
+    reason = None
+    if converged:
+        pass
+    elif entry is None:
+        reason = "is not in the cache"
+    elif entry[1] != total or "sum" not in info:
+        reason = "holds %d bytes, the argument has %d" % (entry[1], total)
+    delta = None
+    tensors = None
+    alloc_error = None
+    if reason is None and not converged:
+        try:
+            if delta_total:
+                delta = _alloc_device_arg(
+                    {"shape": [delta_total]}, torch.uint8, report, keep=base_key
+                )
+            tensors = _alloc_packed_tensors(info, report, keep=base_key)
+        except Exception as e:  # noqa: BLE001 - e.g. out of HBM
+            alloc_error = e  # drain mode below: the frame still has to go
+            delta = None
+    read_ms = ctypes.c_double()
+    h2d_ms = ctypes.c_double()
+    rc = lib.csp_h2d_stream_fd(
+        0, ctypes.c_void_p(delta.data_ptr() if delta is not None else 0),
+        delta_total, _packed_chunk(), -1,
+        ctypes.byref(read_ms), ctypes.byref(h2d_ms),
+    )
+    stage["read_ms"] += read_ms.value
+    stage["h2d_ms"] += h2d_ms.value
+    if rc == 2:
+        # the request stream is no longer aligned: leave, as _receive_device_arg does
+        sys.stderr.write(
+            "csp worker: csp_h2d_stream_fd lost the stream: %s\n"
+            % lib.csp_last_error().decode(errors="replace")
+        )
+        sys.stderr.flush()
+        os._exit(4)
+    if rc == 0:
+        stage["bytes"] += delta_total
+    if converged:
+        return _packed_args_from_cache(lib, index, info, total, new_key, stage, report)
+    if reason is not None:
+        _arg_cache_drop(base_key)
+        report["miss"].append(index)
+        raise RuntimeError(
+            "argument buffer %d: cached argument %s %s" % (index, base_key, reason)
+        )
+    if alloc_error is not None:
+        raise alloc_error
+    if rc != 0:
+        raise RuntimeError(
+            "argument buffer %d: H2D copy failed (rc=%d): %s"
+            % (index, rc, lib.csp_last_error().decode(errors="replace"))
+        )
+    segs = info["packed"]
+    count = len(segs)
+    sizes = [int(seg["nbytes"]) for seg in segs]
+    changed = set(int(j) for j in cache["patch"]["segments"])
+    unchanged = (1 << 64) - 1
+    delta_offs = []
+    patched_bytes = 0
+    for j, n in enumerate(sizes):
+        if j in changed:
+            delta_offs.append(patched_bytes)
+            patched_bytes += (n + 15) // 16 * 16
+        else:
+            delta_offs.append(unchanged)
+    master = entry[0]
+    dst = (ctypes.c_void_p * count)(
+        *[(t.data_ptr() or None) if n else None for t, n in zip(tensors, sizes)]
+    )
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    rc = lib.csp_patch_unpack_checksum_dev(
+        ctypes.c_void_p(master.data_ptr() if total else 0), total,
+        ctypes.c_void_p(delta.data_ptr() if delta is not None else 0), delta_total,
+        dst, (ctypes.c_uint64 * count)(*[int(seg["offset"]) for seg in segs]),
+        (ctypes.c_uint64 * count)(*sizes), (ctypes.c_uint64 * count)(*delta_offs),
+        count, out, ctypes.byref(kernel_ms),
+    )
+    if rc != 0:
+        _arg_cache_drop(base_key)
+        raise RuntimeError(
+            "argument buffer %d: csp_patch_unpack_checksum_dev failed: %s"
+            % (index, lib.csp_last_error().decode(errors="replace"))
+        )
+    got = [int(out[0]), int(out[1])]
+    want = [int(info["sum"][0]), int(info["sum"][1])]
+    if got != want:
+        _arg_cache_drop(base_key)
+        report["miss"].append(index)
+        raise RuntimeError(
+            "argument buffer %d: cached argument %s patched to %s has checksum %r, "
+            "the dispatcher sent %r" % (index, base_key, new_key, got, want)
+        )
+    # the same master under the new key, most recently used; the resident
+    # bytes do not change
+    del _arg_cache[base_key]
+    _arg_cache[new_key] = (master, total, got)
+    report["stored"].append(new_key)
+    report.setdefault("patched", []).append([base_key, new_key])
+    stage["mode"] = "pinned-h2d"
+    stage["tensors"] += 1
+    stage["verified"] += 1
+    stage["packed_tensors"] = stage.get("packed_tensors", 0) + count
+    stage["packed_bytes"] = stage.get("packed_bytes", 0) + sum(sizes)
+    stage["patched_segments"] = stage.get("patched_segments", 0) + len(changed)
+    stage["patched_bytes"] = stage.get("patched_bytes", 0) + delta_total
+    stage["patch_ms"] = round(stage.get("patch_ms", 0.0) + kernel_ms.value, 3)
+    return tensors
+
+
 def _receive_packed_device_args(index, info, stage, report):
     """Persistent mode: a ``packed`` device entry.  Its one frame lands in
     HBM as one arena through csp_h2d_stream_fd, and ONE
@@ -925,7 +1085,9 @@ def _receive_packed_device_args(index, info, stage, report):
     With ``"cache": {"key", "store": true}`` the arena is a new master that
     stays in HBM under the key; with ``{"key", "ref": true}`` there is no
     frame and the tensors are unpacked from the master already held
-    (_packed_args_from_cache).  A transient arena is let go before user code
+    (_packed_args_from_cache); with ``{"key", "patch": {"base", "segments"}}``
+    the frame is a delta that is applied to the master held under ``base``
+    (_patch_packed_args).  A transient arena is let go before user code
     runs.  Whatever goes wrong short of a broken stream, the frame is
     consumed before the error is raised, as in _receive_device_arg."""
     global _arg_cache_resident
@@ -947,6 +1109,8 @@ def _receive_packed_device_args(index, info, stage, report):
         return _packed_args_from_cache(
             lib, index, info, total, cache["key"], stage, report
         )
+    if cache.get("patch"):
+        return _patch_packed_args(lib, index, info, total, cache, stage, report)
     key = None
     master = None
     if cache.get("store") and "sum" in info and total:

@@ -41,6 +41,11 @@ class WorkerHandle:
     #: in HBM (``cache_tensor_args``).  A new handle starts empty, so a
     #: worker that died or was respawned is assumed to hold nothing.
     resident: Set[str] = field(default_factory=set)
+    #: for the packed arenas among them that were sent with
+    #: ``patch_tensor_args`` on: key -> ``((segment_key, nbytes), ...)``, what
+    #: a later arena of the same layout is compared with to send a delta.
+    #: Maintained wherever ``resident`` is.
+    resident_arenas: Dict[str, tuple] = field(default_factory=dict)
 
     @property
     def alive(self) -> bool:
@@ -270,11 +275,18 @@ def packed_content_key(segment_keys) -> str:
 
 
 def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
-                     buffers, buffer_meta):
+                     buffers, buffer_meta, patch_max_fraction=None):
     """The ``pack_tensor_args`` half of :func:`extract_arg_buffers`: emit the
     packed entry when the rule in its docstring holds.  Returns
     ``{id(tensor): marker}``, empty when nothing is packed.  Only called with
-    the option on, so the per-tensor path pays nothing for it."""
+    the option on, so the per-tensor path pays nothing for it.
+
+    With ``patch_max_fraction`` (``patch_tensor_args``) a cached entry's
+    ``"cache"`` also keeps, for the dispatcher alone (:class:`_ArgCacheSend`
+    rebuilds ``"cache"`` for the wire), ``"segments"``: the per-segment
+    ``(content key, nbytes)``, ``"seg_parts"``: per segment its parts of the
+    frame (the tensor's own memory and its zero padding), and the
+    fraction."""
     import ctypes
 
     import torch
@@ -317,12 +329,15 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
     srcs = [t.contiguous() for t in tensors]
     parts = []
     views = []
+    seg_parts = []
     for src_t, n in zip(srcs, sizes):
         view = (ctypes.c_char * n).from_address(src_t.data_ptr()) if n else b""
         views.append(view)
         parts.append(view)
+        seg_parts.append([view])
         if n % PACK_ALIGN:
             parts.append(bytes(PACK_ALIGN - n % PACK_ALIGN))
+            seg_parts[-1].append(parts[-1])
     info = {
         "device": True,
         "packed": [
@@ -338,12 +353,16 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
         s0, s1 = compose_packed_checksum(sums, offsets)
         info["sum"] = [int(s0), int(s1)]
         if cache_min_bytes is not None and total >= max(1, cache_min_bytes):
-            info["cache"] = {
-                "key": packed_content_key(
-                    (tensor_content_key(t, v), n)
-                    for t, v, n in zip(tensors, views, sizes)
+            segment_keys = tuple(
+                (tensor_content_key(t, v), n)
+                for t, v, n in zip(tensors, views, sizes)
+            )
+            info["cache"] = {"key": packed_content_key(segment_keys)}
+            if patch_max_fraction is not None:
+                info["cache"].update(
+                    segments=segment_keys, seg_parts=seg_parts,
+                    patch_max_fraction=float(patch_max_fraction),
                 )
-            }
     # the source tensors stay alive until the frame is drained
     buffers.append((FrameParts(parts), srcs))
     buffer_meta.append(info)
@@ -357,6 +376,7 @@ def extract_arg_buffers(
     args, kwargs, threshold: int, to_device: bool = False,
     cache_min_bytes: Optional[int] = None,
     pack_min_bytes: Optional[int] = None,
+    patch_max_fraction: Optional[float] = None,
 ):
     """Pull large contiguous CPU torch tensors out of (args, kwargs) and
     replace them with out-of-band buffer markers (the request-direction
@@ -395,7 +415,14 @@ def extract_arg_buffers(
     one segment and one marker.  With the cache on and
     ``total >= cache_min_bytes`` the entry carries ``"cache": {"key"}`` from
     :func:`packed_content_key`.  Otherwise every tensor takes the per-tensor
-    path, exactly as without the option."""
+    path, exactly as without the option.
+
+    ``patch_max_fraction`` (the executor's ``patch_tensor_args`` and
+    ``patch_args_max_fraction``; ``None`` is off): a cached packed entry also
+    keeps its per-segment keys and parts on the dispatcher side, so that
+    :func:`run_task` can send it as a delta against an arena of the same
+    layout that the worker holds (:class:`_ArgCacheSend`).  Nothing of it
+    reaches the wire."""
     import sys
 
     if "torch" not in sys.modules:
@@ -409,7 +436,8 @@ def extract_arg_buffers(
     packed_markers = None  # id(tensor) -> marker, with pack_tensor_args
     if to_device and pack_min_bytes is not None:
         packed_markers = _pack_small_args(
-            args, kwargs, threshold, cache_min_bytes, pack_min_bytes, buffers, buffer_meta
+            args, kwargs, threshold, cache_min_bytes, pack_min_bytes, buffers, buffer_meta,
+            patch_max_fraction=patch_max_fraction,
         )
 
     def extract(t):
@@ -573,40 +601,111 @@ class _ArgCacheSend:
         self.cache_stats = cache_stats
         self.keys = [(info.get("cache") or {}).get("key") for info in entries]
         self.refs = [False] * len(entries)
+        #: per entry ``(base key, changed segment indices, delta FrameParts)``
+        #: when the last :meth:`frames` sent it as a patch, else None
+        self.patches = [None] * len(entries)
+
+    def _plan_patch(self, cache):
+        """``patch_tensor_args``: the delta that turns an arena the worker
+        holds into this one, or None.  Among the resident arenas with the
+        same byte counts in the same order, the one with the fewest changed
+        rounded bytes; a patch only when they are more than none and at most
+        ``patch_max_fraction`` of the arena."""
+        segments = cache["segments"]
+        sizes = [n for _key, n in segments]
+        best = None
+        for base, held in self.handle.resident_arenas.items():
+            if base not in self.handle.resident or len(held) != len(segments):
+                continue
+            if any(n != m for n, (_key, m) in zip(sizes, held)):
+                continue
+            changed = [j for j, (new, old) in enumerate(zip(segments, held)) if new[0] != old[0]]
+            nbytes = sum(-(-sizes[j] // PACK_ALIGN) * PACK_ALIGN for j in changed)
+            if best is None or nbytes < best[0]:
+                best = (nbytes, base, changed)
+        if best is None:
+            return None
+        nbytes, base, changed = best
+        total = sum(-(-n // PACK_ALIGN) * PACK_ALIGN for n in sizes)
+        if not 0 < nbytes <= cache["patch_max_fraction"] * total:
+            return None
+        # cut from the tensors' own memory and the zero padding: no host copy
+        delta = FrameParts([p for j in changed for p in cache["seg_parts"][j]])
+        return base, changed, delta
+
+    def _now_resident(self, index, key):
+        """``key``'s frame has been written: the worker holds it from here on
+        as far as later requests on this channel are concerned."""
+        self.handle.resident.add(key)
+        segments = (self.entries[index].get("cache") or {}).get("segments")
+        if segments is not None:
+            self.handle.resident_arenas[key] = segments
+
+    def _forget(self, key):
+        self.handle.resident.discard(key)
+        self.handle.resident_arenas.pop(key, None)
 
     def frames(self, full: bool):
         """The request's frames.  A generator: the channel runs it frame by
         frame under its write lock, so the decisions are taken in send
-        order.  ``full``: no references, every entry with its frame."""
+        order.  ``full``: no references and no patches, every entry with its
+        frame."""
         resident = self.handle.resident
         self.refs = [
             key is not None and not full and key in resident for key in self.keys
         ]
+        self.patches = [None] * len(self.entries)
         wire = []
-        for info, key, ref in zip(self.entries, self.keys, self.refs):
+        for index, (info, key, ref) in enumerate(zip(self.entries, self.keys, self.refs)):
             if key is not None:
+                cache = info["cache"]
                 info = dict(info)
-                info["cache"] = {"key": key, "ref" if ref else "store": True}
+                if not ref and not full and cache.get("segments") is not None:
+                    self.patches[index] = self._plan_patch(cache)
+                patch = self.patches[index]
+                if patch is not None:
+                    info["cache"] = {
+                        "key": key, "patch": {"base": patch[0], "segments": patch[1]},
+                    }
+                    info["patch_nbytes"] = patch[2].nbytes
+                else:
+                    info["cache"] = {"key": key, "ref" if ref else "store": True}
             wire.append(info)
         yield cloudpickle.dumps(dict(self.base, arg_buffers=wire))
-        for view, key, ref in zip(self.views, self.keys, self.refs):
+        for index, (view, key, ref) in enumerate(zip(self.views, self.keys, self.refs)):
             if ref:
                 continue
-            yield view
+            patch = self.patches[index]
+            yield view if patch is None else patch[2]
+            if patch is not None:
+                self._forget(patch[0])  # patched in place: the base is gone
             if key is not None:
-                resident.add(key)  # its frame has been written
+                self._now_resident(index, key)  # its frame has been written
 
     def reconcile(self, meta) -> bool:
         """Bring ``handle.resident`` in line with the worker's report and
-        count; returns whether the worker missed a reference."""
+        count; returns whether the worker missed a reference or the base of
+        a patch."""
         report = meta.get("arg_cache") or {}
         held = set(report.get("stored") or ()) | set(report.get("hits") or ())
         for key in self.keys:
             if key is not None and key not in held:
-                self.handle.resident.discard(key)
+                self._forget(key)
         missed = [i for i in (report.get("miss") or ()) if 0 <= i < len(self.keys)]
+        for i in missed:
+            if self.patches[i] is not None:
+                # a failed patch in place: the worker let the base go
+                self._forget(self.patches[i][0])
+        done = {tuple(pair) for pair in (report.get("patched") or ())}
         stats = self.cache_stats
         if stats is not None:
+            for view, key, patch in zip(self.views, self.keys, self.patches):
+                if patch is not None and (patch[0], key) in done:
+                    stats["arg_cache_patches"] = stats.get("arg_cache_patches", 0) + 1
+                    stats["arg_cache_bytes_saved"] = (
+                        stats.get("arg_cache_bytes_saved", 0)
+                        + _view_nbytes(view) - patch[2].nbytes
+                    )
             for view, key, ref in zip(self.views, self.keys, self.refs):
                 if ref and key in held:
                     stats["arg_cache_hits"] = stats.get("arg_cache_hits", 0) + 1
@@ -650,6 +749,18 @@ async def run_task(
     task is sent once more with full frames.  ``cache_stats`` (a mutable
     dict, the executor's counters) gets ``arg_cache_hits``,
     ``arg_cache_misses`` and ``arg_cache_bytes_saved``.
+
+    A packed entry that keeps its per-segment keys (``patch_tensor_args``)
+    and whose key is not resident is compared, in the same place, with the
+    arenas of the same layout in ``handle.resident_arenas``: when at most
+    ``patch_max_fraction`` of its bytes differ from one of them it travels
+    as ``{"key", "patch": {"base", "segments"}}`` with a frame of only the
+    changed segments, the worker patches the held arena in place, and from
+    the moment that frame has been written the base is no longer resident
+    and the new key is.  A missing base is a miss like a missing reference;
+    the resend never patches.  ``cache_stats`` also gets
+    ``arg_cache_patches``, and ``arg_cache_bytes_saved`` grows by the arena
+    bytes that the delta left out.
     """
     entries = arg_buffer_meta or []
     cache = None

@@ -151,6 +151,18 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # dispatch there (0.89 against 1.76 ms), and no larger measured total
     # has it slower.  Below 64 KiB nothing was measured.
     "pack_args_min_bytes": 65536,
+    # With cache_tensor_args and pack_tensor_args: a packed argument arena
+    # with the layout of an arena that the worker already holds (a frozen
+    # base plus a few adapter, optimizer or step tensors that change every
+    # dispatch) travels as a delta of only the changed tensors.  The worker
+    # patches the held arena in place, in the same kernel launch that
+    # scatters and verifies it, and holds it under the new key.
+    "patch_tensor_args": False,
+    # Patch only when the changed tensors are at most this fraction of the
+    # arena, else send it whole.  0.5 is a policy default, not a
+    # measurement: a patch always sends fewer bytes than a store, but it
+    # consumes the base, which a store would have left in the cache.
+    "patch_args_max_fraction": 0.5,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -349,6 +361,8 @@ class SSHExecutor(RemoteExecutor):
         arg_cache_min_bytes: Optional[int] = None,
         pack_tensor_args: Optional[bool] = None,
         pack_args_min_bytes: Optional[int] = None,
+        patch_tensor_args: Optional[bool] = None,
+        patch_args_max_fraction: Optional[float] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -457,6 +471,22 @@ class SSHExecutor(RemoteExecutor):
         )
         if self.pack_args_min_bytes < 0:
             raise ValueError("pack_args_min_bytes must not be negative")
+        self.patch_tensor_args = bool(
+            _conf("patch_tensor_args", patch_tensor_args, default=False)
+        )
+        if self.patch_tensor_args and not (
+            self.cache_tensor_args and self.pack_tensor_args
+        ):
+            raise ValueError(
+                "patch_tensor_args needs cache_tensor_args=True and "
+                "pack_tensor_args=True: it patches a packed argument arena "
+                "that the worker holds in its cache"
+            )
+        self.patch_args_max_fraction = float(
+            _conf("patch_args_max_fraction", patch_args_max_fraction, default=0.5)
+        )
+        if not 0.0 < self.patch_args_max_fraction <= 1.0:
+            raise ValueError("patch_args_max_fraction must be in (0, 1]")
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -498,6 +528,9 @@ class SSHExecutor(RemoteExecutor):
             "arg_cache_hits": 0,
             "arg_cache_misses": 0,
             "arg_cache_bytes_saved": 0,
+            # patch_tensor_args: packed arenas sent as a delta against an
+            # arena the worker held (the bytes left out count as saved)
+            "arg_cache_patches": 0,
         }
 
     # ------------------------------------------------------------------
@@ -1332,6 +1365,11 @@ class SSHExecutor(RemoteExecutor):
                             pack_min_bytes=(
                                 self.pack_args_min_bytes
                                 if self.pack_tensor_args
+                                else None
+                            ),
+                            patch_max_fraction=(
+                                self.patch_args_max_fraction
+                                if self.patch_tensor_args
                                 else None
                             ),
                         )
