@@ -19,6 +19,10 @@ gfx950 only) provides:
 * ``csp_patch_unpack_checksum_dev`` — the same launch on a held arena, with
   the changed segments written over it in place from a small delta arena
   (``patch_tensor_args``),
+* ``csp_rebase_unpack_checksum_dev`` — the same launch for a new arena of any
+  layout, each segment from a held arena or from a small delta arena, written
+  out as a new master while the held one is only read
+  (``rebase_tensor_args``),
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
   ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
@@ -163,6 +167,23 @@ def load(path: str = "") -> ctypes.CDLL:
         ctypes.c_void_p,
         ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_rebase_unpack_checksum_dev.restype = ctypes.c_int
+    lib.csp_rebase_unpack_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
@@ -474,9 +495,60 @@ def patch_unpack_checksum_device(
     return {"sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
 
 
+def rebase_unpack_checksum_device(
+    base_ptr: int, base_bytes: int, delta_ptr: int, delta_bytes: int,
+    out_arena_ptr: int, arena_bytes: int, segments,
+) -> dict:
+    """Build a NEW arena from a held one plus a delta, scatter it and checksum
+    it in one kernel launch (``rebase_tensor_args``).  ``segments`` is a
+    sequence of ``(dst_ptr, out_off, nbytes, base_off_or_None,
+    delta_off_or_None)`` with exactly one source each: ``out_off`` follows
+    :func:`pack_layout` for the new arena of ``arena_bytes``; a ``base_off``
+    is any 16-byte multiple inside the base arena (any order, shared between
+    segments); the delta-sourced segments, in order, follow
+    :func:`pack_layout` inside the delta and total ``delta_bytes``.  Every
+    16-byte vector a segment owns is loaded once, written to the new master
+    at ``out_arena_ptr`` (padding as the source has it), scattered to
+    ``dst_ptr`` and summed with its word index in the new arena.
+    ``out_arena_ptr == 0`` is a transient rebase: the same scatter and sum,
+    no new master.  Base and delta are only read.  A layout violation, a
+    misaligned pointer, or an overlap of the new master or a destination with
+    anything it must not touch raises ``GpuLibError`` and launches nothing.
+    Returns ``{"sum": (s0, s1), "kernel_ms": ...}``: the sum is
+    :func:`checksum_device` of the new arena.  Shares the grid cap of
+    :func:`unpack_checksum_grid_cap`.  Runs on the library's copy stream;
+    work on the buffers on another stream must be complete
+    (``torch.cuda.synchronize()``) first."""
+    lib = load()
+    n = len(segments)
+    dst = (ctypes.c_void_p * n)(*[int(s[0]) or None for s in segments])
+    off = (ctypes.c_uint64 * n)(*[int(s[1]) for s in segments])
+    size = (ctypes.c_uint64 * n)(*[int(s[2]) for s in segments])
+    base_off = (ctypes.c_uint64 * n)(
+        *[PATCH_UNCHANGED if s[3] is None else int(s[3]) for s in segments]
+    )
+    delta_off = (ctypes.c_uint64 * n)(
+        *[PATCH_UNCHANGED if s[4] is None else int(s[4]) for s in segments]
+    )
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_rebase_unpack_checksum_dev(
+            ctypes.c_void_p(base_ptr or None), base_bytes,
+            ctypes.c_void_p(delta_ptr or None), delta_bytes,
+            ctypes.c_void_p(out_arena_ptr or None), arena_bytes,
+            dst, off, size, base_off, delta_off, n, out, ctypes.byref(kernel_ms),
+        ),
+        "csp_rebase_unpack_checksum_dev",
+    )
+    return {"sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
+
+
 def unpack_checksum_grid_cap(cap: int = 0) -> int:
-    """Tools only: set the grid cap of :func:`unpack_checksum_device` and
-    :func:`patch_unpack_checksum_device` (0 restores the shipped default).
+    """Tools only: set the grid cap of :func:`unpack_checksum_device`,
+    :func:`patch_unpack_checksum_device` and
+    :func:`rebase_unpack_checksum_device` (0 restores the shipped default).
     Returns the cap in effect."""
     return int(load().csp_unpack_checksum_grid_cap(int(cap)))
 

@@ -41,14 +41,21 @@
 //                       small delta arena, are written over the held master
 //                       in place while the whole new arena is scattered and
 //                       checksummed,
+//   * csp_rebase_unpack_checksum_dev
+//                     — the same pass for a NEW arena of any layout: every
+//                       segment comes from a held arena, wherever it lies
+//                       there, or from a small delta arena, and the new arena
+//                       is written out as a new master while it is scattered
+//                       and checksummed; the held arena is only read,
 //   * csp_hbm_sweep_dev
 //                     — one launch of the probe's HBM sweep kernel on the
 //                       caller's buffers (tests: what the sweep copies),
 //   * csp_checksum_grid_cap / csp_copy_checksum_grid_cap /
 //     csp_unpack_checksum_grid_cap
 //                     — tools only: the grid caps of the checksum, copy and
-//                       unpack kernels (the patch kernel shares the unpack
-//                       kernel's), so tests reach every loop on tiny data.
+//                       unpack kernels (the patch and rebase kernels share the
+//                       unpack kernel's), so tests reach every loop on tiny
+//                       data.
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -1959,6 +1966,402 @@ extern "C" int csp_patch_unpack_checksum_dev(void* master, size_t arena_bytes,
         *kernel_ms = ms;
     }
 #undef PATCH_TRY
+    out[0] = host[0];
+    out[1] = host[1];
+    return done(0);
+}
+
+// ---------------------------------------------------------------------------
+// Argument rebasing: a new master built from a held arena plus a delta
+// ---------------------------------------------------------------------------
+//
+// The patch above consumes its base and needs the same layout.  A rebase
+// builds a NEW arena of any layout and leaves the base alone: every segment
+// of the new arena comes either from the base, at whatever 16-byte aligned
+// offset it has there, or from a small delta arena, and the one pass that
+// scatters and verifies the new arena also writes it out as a new master.
+//
+// Layout: out_off, nbytes, dst and arena_bytes follow the unpack layout rule
+// for the NEW arena.  Exactly one of base_off[k] and delta_off[k] differs
+// from UINT64_MAX.  The delta-sourced segments, in segment order, obey the
+// pack layout inside the delta; base offsets are free: any order, shared by
+// several new segments, base segments left out.
+//
+//   - the unpack and patch kernels' decomposition, unchanged: tiles of
+//     kPackTileBytes of one segment, the host-built tile prefix, a binary
+//     search per tile that depends on the tile index only, per-lane u64 s0/t
+//     accumulators carried across a block's tiles, wave shuffles, LDS, one
+//     atomicAdd pair per block, 256-thread blocks, the unpack kernel's grid
+//     cap;
+//   - the table entry holds an absolute source pointer and a from_delta flag:
+//     delta loads are nontemporal (read once), base loads are plain (the base
+//     is re-read by later hits); the choice is per tile and wave-uniform;
+//   - every vector a segment owns is loaded once, stored whole to
+//     out_arena + out_off with a plain aligned 16-byte store (the new master
+//     is re-read by the next hit; the last vector's padding goes in as the
+//     source has it), stored to dst by the unpack rules and summed with the
+//     word index global to the new arena;
+//   - out_arena == nullptr is a transient rebase: the same scatter and sum,
+//     no new master written; the branch is on a kernel argument, so uniform;
+//   - base and delta are never written, and the host refuses an out_arena
+//     that overlaps either or any dst, so no lane reads what another writes.
+struct RebaseSeg {
+    unsigned char* dst;
+    const unsigned char* src;  // absolute: into the base or into the delta
+    unsigned long long out_off;
+    unsigned long long nbytes;
+    unsigned long long tile_begin;  // tiles owned by the segments before this one
+    unsigned long long from_delta;  // nonzero: src is in the delta
+};
+
+__global__ __launch_bounds__(256) void csp_rebase_unpack_checksum_kernel(
+    const RebaseSeg* __restrict__ segs, unsigned int nseg, size_t total_tiles,
+    unsigned char* out_arena, unsigned long long* __restrict__ out) {
+    unsigned long long s0 = 0, t = 0;
+    const bool keep = out_arena != nullptr;  // kernel argument: uniform
+    for (size_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+        // last segment whose first tile is <= tile (tile_begin is strictly
+        // increasing: the host leaves zero-byte segments out of the table)
+        unsigned int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].tile_begin <= tile) lo = mid; else hi = mid;
+        }
+        const RebaseSeg s = segs[lo];
+        const CSP_GLOBAL u32x4* src = reinterpret_cast<const CSP_GLOBAL u32x4*>(
+            (const CSP_GLOBAL unsigned char*)s.src);
+        CSP_GLOBAL u32x4* mst = reinterpret_cast<CSP_GLOBAL u32x4*>(
+            (CSP_GLOBAL unsigned char*)(out_arena + s.out_off));
+        const bool from_delta = s.from_delta != 0;  // per tile: wave-uniform
+        const unpack_dst_t dst = (unpack_dst_t)s.dst;
+        const size_t nfull = s.nbytes / 16;  // vectors wholly inside the segment
+        const unsigned int tail = (unsigned int)(s.nbytes % 16);
+        const size_t nvec = nfull + (tail ? 1 : 0);  // vectors the segment owns
+        const size_t v0 = (tile - s.tile_begin) * kPackTileVecs + threadIdx.x;
+        // new-arena-global index of the segment's first word, modulo 2^32
+        // like csp_checksum_kernel's (unsigned int)(i * 4)
+        const unsigned int word_base = (unsigned int)(s.out_off / 4);
+        if ((tile - s.tile_begin + 1) * kPackTileVecs <= nfull) {
+            // interior tile: every lane has four whole vectors
+            u32x4 v[kPackUnroll];
+            if (from_delta) {
+#pragma unroll
+                for (int u = 0; u < kPackUnroll; ++u)
+                    v[u] = __builtin_nontemporal_load(&src[v0 + u * 256]);
+            } else {
+#pragma unroll
+                for (int u = 0; u < kPackUnroll; ++u) v[u] = src[v0 + u * 256];
+            }
+            if (keep) {
+#pragma unroll
+                for (int u = 0; u < kPackUnroll; ++u) mst[v0 + u * 256] = v[u];
+            }
+#pragma unroll
+            for (int u = 0; u < kPackUnroll; ++u) {
+                const size_t vi = v0 + u * 256;
+                __builtin_nontemporal_store(
+                    v[u], reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+                checksum_add(s0, t, v[u], word_base + (unsigned int)(vi * 4));
+            }
+            continue;
+        }
+#pragma unroll
+        for (int u = 0; u < kPackUnroll; ++u) {
+            const size_t vi = v0 + u * 256;
+            if (vi >= nvec) continue;
+            u32x4 v;  // padding included: all 16 bytes are base or delta
+            if (from_delta)
+                v = __builtin_nontemporal_load(&src[vi]);
+            else
+                v = src[vi];
+            if (keep) mst[vi] = v;
+            checksum_add(s0, t, v, word_base + (unsigned int)(vi * 4));
+            if (vi < nfull)
+                __builtin_nontemporal_store(
+                    v, reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+            else
+                unpack_store_tail(dst + vi * 16, v, tail);
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+// Build the new arena's nseg segments (layout rule above) from the base and
+// the delta, scatter them to dst[k], write them to out_arena unless it is
+// null, and put csp_checksum_dev's (s0, s1) of the new arena into out[2].
+// Returns -1 with a message and launches nothing for every refusal of
+// csp_unpack_checksum_dev on the new layout (out_off in the place of its
+// src_off) and for: a misaligned base, delta or out_arena; a base_off that is
+// not a multiple of 16 or with base_off + round_up(nbytes, 16) > base_bytes; a
+// segment with both sources or with neither; a delta_off that breaks the
+// delta layout rule or a delta_bytes that is not its total; a null base or
+// delta where bytes are to come from it; an overflow; out_arena overlapping
+// the base, the delta or any dst; any dst overlapping the base or the delta.
+// Ranges that merely touch are accepted, and so are base and delta ranges
+// that overlap each other: both are only read.  Overlap between destinations
+// is the caller's responsibility, as in the unpack.  Shares the unpack
+// kernel's grid cap (csp_unpack_checksum_grid_cap).  Runs on copy_stream()
+// and synchronises it before returning.  kernel_ms (optional): the kernel
+// alone, from events around the launch.
+extern "C" int csp_rebase_unpack_checksum_dev(const void* base, size_t base_bytes,
+                                              const void* delta, size_t delta_bytes,
+                                              void* out_arena, size_t arena_bytes,
+                                              void* const* dst, const uint64_t* out_off,
+                                              const uint64_t* nbytes,
+                                              const uint64_t* base_off,
+                                              const uint64_t* delta_off, size_t nseg,
+                                              uint64_t out[2], double* kernel_ms) {
+    static const char* const fn = "csp_rebase_unpack_checksum_dev";
+    out[0] = out[1] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+    const uintptr_t p = reinterpret_cast<uintptr_t>(delta);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(out_arena);
+    if (b % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: base pointer %p is not 16-byte aligned", fn, base);
+        return -1;
+    }
+    if (p % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: delta pointer %p is not 16-byte aligned", fn,
+                 delta);
+        return -1;
+    }
+    if (a % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: out_arena pointer %p is not 16-byte aligned", fn,
+                 out_arena);
+        return -1;
+    }
+    if (nseg >= (size_t(1) << 31)) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu segments are too many", fn, nseg);
+        return -1;
+    }
+    if (b + base_bytes < b) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at base %p overflow", fn, base_bytes,
+                 base);
+        return -1;
+    }
+    if (p + delta_bytes < p) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at delta %p overflow", fn, delta_bytes,
+                 delta);
+        return -1;
+    }
+    if (a + arena_bytes < a) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at out_arena %p overflow", fn,
+                 arena_bytes, out_arena);
+        return -1;
+    }
+    std::vector<RebaseSeg> table;
+    table.reserve(nseg);
+    uint64_t expect = 0, delta_expect = 0, tiles = 0;
+    bool base_used = false;
+    for (size_t k = 0; k < nseg; ++k) {
+        if (out_off[k] != expect) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: out_off[%zu] is %llu, the layout rule gives %llu", fn, k,
+                     (unsigned long long)out_off[k], (unsigned long long)expect);
+            return -1;
+        }
+        const uint64_t rounded = (nbytes[k] + 15) & ~uint64_t(15);
+        if (rounded < nbytes[k] || expect + rounded < expect) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu overflows", fn, k);
+            return -1;
+        }
+        expect += rounded;
+        const bool from_base = base_off[k] != UINT64_MAX;
+        const bool from_delta = delta_off[k] != UINT64_MAX;
+        if (from_base == from_delta) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu has %s", fn, k,
+                     from_base ? "both a base_off and a delta_off"
+                               : "neither a base_off nor a delta_off");
+            return -1;
+        }
+        if (from_delta) {
+            if (delta_off[k] != delta_expect) {
+                snprintf(g_err, sizeof(g_err),
+                         "%s: delta_off[%zu] is %llu, the delta layout rule gives %llu", fn, k,
+                         (unsigned long long)delta_off[k], (unsigned long long)delta_expect);
+                return -1;
+            }
+            delta_expect += rounded;  // <= expect: cannot overflow
+        } else {
+            if (base_off[k] % 16 != 0) {
+                snprintf(g_err, sizeof(g_err),
+                         "%s: base_off[%zu] is %llu, not a multiple of 16", fn, k,
+                         (unsigned long long)base_off[k]);
+                return -1;
+            }
+            if (base_off[k] > (uint64_t)base_bytes ||
+                rounded > (uint64_t)base_bytes - base_off[k]) {
+                snprintf(g_err, sizeof(g_err),
+                         "%s: base_off[%zu] %llu with %llu rounded bytes exceeds the base's %zu",
+                         fn, k, (unsigned long long)base_off[k], (unsigned long long)rounded,
+                         base_bytes);
+                return -1;
+            }
+        }
+        const uintptr_t d = reinterpret_cast<uintptr_t>(dst[k]);
+        if (d % 16 != 0) {
+            snprintf(g_err, sizeof(g_err), "%s: dst[%zu] %p is not 16-byte aligned", fn, k,
+                     dst[k]);
+            return -1;
+        }
+        if (nbytes[k] == 0) continue;  // owns no tile
+        if (d == 0) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu has %llu bytes and a null dst", fn,
+                     k, (unsigned long long)nbytes[k]);
+            return -1;
+        }
+        if (d + nbytes[k] < d) {
+            snprintf(g_err, sizeof(g_err), "%s: dst[%zu] %p with %llu bytes overflows", fn, k,
+                     dst[k], (unsigned long long)nbytes[k]);
+            return -1;
+        }
+        if (from_base) base_used = true;
+        table.push_back({static_cast<unsigned char*>(dst[k]),
+                         from_delta ? static_cast<const unsigned char*>(delta) + delta_off[k]
+                                    : static_cast<const unsigned char*>(base) + base_off[k],
+                         out_off[k], nbytes[k], tiles, from_delta ? 1ull : 0ull});
+        tiles += (rounded + kPackTileBytes - 1) / kPackTileBytes;
+    }
+    if (expect != (uint64_t)arena_bytes) {
+        snprintf(g_err, sizeof(g_err), "%s: arena_bytes is %zu, the segments need %llu", fn,
+                 arena_bytes, (unsigned long long)expect);
+        return -1;
+    }
+    if (delta_expect != (uint64_t)delta_bytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: delta_bytes is %zu, the delta-sourced segments need %llu", fn,
+                 delta_bytes, (unsigned long long)delta_expect);
+        return -1;
+    }
+    if (arena_bytes == 0) return 0;
+    if (base == nullptr && base_used) {
+        snprintf(g_err, sizeof(g_err), "%s: null base for base-sourced segments", fn);
+        return -1;
+    }
+    if (delta == nullptr && delta_bytes != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: null delta for %zu bytes", fn, delta_bytes);
+        return -1;
+    }
+    if (out_arena != nullptr) {
+        if (base_bytes != 0 && a < b + base_bytes && b < a + arena_bytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: %zu bytes at out_arena %p overlap the base at %p", fn, arena_bytes,
+                     out_arena, base);
+            return -1;
+        }
+        if (delta_bytes != 0 && a < p + delta_bytes && p < a + arena_bytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: %zu bytes at out_arena %p overlap the delta at %p", fn, arena_bytes,
+                     out_arena, delta);
+            return -1;
+        }
+    }
+    for (size_t k = 0; k < table.size(); ++k) {
+        const uintptr_t d = reinterpret_cast<uintptr_t>(table[k].dst);
+        if (out_arena != nullptr && d < a + arena_bytes && a < d + table[k].nbytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: %llu bytes at dst %p overlap the out_arena at %p", fn,
+                     (unsigned long long)table[k].nbytes, (void*)table[k].dst, out_arena);
+            return -1;
+        }
+        if (base_bytes != 0 && d < b + base_bytes && b < d + table[k].nbytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: %llu bytes at dst %p overlap the base at %p", fn,
+                     (unsigned long long)table[k].nbytes, (void*)table[k].dst, base);
+            return -1;
+        }
+        if (delta_bytes != 0 && d < p + delta_bytes && p < d + table[k].nbytes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: %llu bytes at dst %p overlap the delta at %p", fn,
+                     (unsigned long long)table[k].nbytes, (void*)table[k].dst, delta);
+            return -1;
+        }
+    }
+
+    // one accumulator pair and one grow-only table per process, one call at
+    // a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static RebaseSeg* dev_table = nullptr;
+    static size_t dev_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_device != device) {
+        if (acc) (void)hipFree(acc);
+        if (dev_table) (void)hipFree(dev_table);
+        acc = nullptr;
+        dev_table = nullptr;
+        dev_cap = 0;
+        dev_device = device;
+    }
+    if (acc == nullptr) HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+    if (dev_table == nullptr || dev_cap < table.size()) {
+        if (dev_table) (void)hipFree(dev_table);
+        dev_table = nullptr;
+        dev_cap = 0;
+        size_t cap = 1024;
+        while (cap < table.size()) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_table, cap * sizeof(RebaseSeg)));
+        dev_cap = cap;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define REBASE_TRY(expr)                                           \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    // `table` outlives the copy: the stream is synchronised below
+    REBASE_TRY(hipMemcpyAsync(dev_table, table.data(), table.size() * sizeof(RebaseSeg),
+                              hipMemcpyHostToDevice, s));
+    REBASE_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t blocks = tiles < g_unpack_grid_cap ? (size_t)tiles : g_unpack_grid_cap;
+    if (t0) REBASE_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_rebase_unpack_checksum_kernel, dim3((unsigned int)blocks),
+                       dim3(256), 0, s, dev_table, (unsigned int)table.size(), (size_t)tiles,
+                       static_cast<unsigned char*>(out_arena), acc);
+    REBASE_TRY(hipGetLastError());
+    if (t1) REBASE_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    REBASE_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    REBASE_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        REBASE_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef REBASE_TRY
     out[0] = host[0];
     out[1] = host[1];
     return done(0);

@@ -56,7 +56,19 @@ Protocol (all frames: 8-byte big-endian length + payload):
              new arena and yields its checksum in one pass; the master is
              then held under NEW and meta["arg_cache"]["patched"] lists
              [BASE, NEW].  An absent BASE or a wrong checksum is a miss
-             like a missed "ref", and the master goes.
+             like a missed "ref", and the master goes.  With the executor
+             option rebase_tensor_args it carries instead "cache": {"key":
+             NEW, "rebase": {"base": BASE, "base_nbytes": N, "sources":
+             [...]}} and "rebase_nbytes": sources[j] is segment j's offset
+             in the arena of N bytes held under BASE, whatever that
+             arena's layout, or -1 when its bytes are in the ONE frame, a
+             delta arena of rebase_nbytes bytes with those segments in
+             order.  csp_rebase_unpack_checksum_dev builds a NEW master
+             from both, scatters it and yields its checksum in one pass;
+             BASE stays in the cache and meta["arg_cache"]["rebased"]
+             lists [BASE, NEW].  When the budget cannot hold both, no
+             master is written and NEW is in "not_stored".  An absent
+             BASE or a wrong checksum is a miss, and BASE goes.
   ack    = pickle tuple ("A1", op_id) — written as soon as the request
              (and its arg frames) has been fully received, BEFORE any
              user code runs.  The dispatcher uses it to distinguish
@@ -271,6 +283,23 @@ def _load_gpu_lib():
         ctypes.c_void_p,
         ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_rebase_unpack_checksum_dev.restype = ctypes.c_int
+    lib.csp_rebase_unpack_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_uint64),
@@ -671,16 +700,22 @@ def _arg_cache_evict_all(report, keep=None):
     return bool(victims)
 
 
-def _arg_cache_new_master(nbytes, report):
+def _arg_cache_new_master(nbytes, report, keep=None):
     """A master of ``nbytes`` within ARG_CACHE_BYTES, least recently used
     entries evicted to make room; None when it does not fit the budget or
-    the device has no room for it."""
+    the device has no room for it.  ``keep``: a key that is never evicted
+    (the base of a rebase); None as well when the budget cannot hold it and
+    the new master together, and then nothing is evicted."""
     import torch
 
     if nbytes > ARG_CACHE_BYTES:
         return None
+    if keep is not None and keep in _arg_cache:
+        if _arg_cache[keep][1] + nbytes > ARG_CACHE_BYTES:
+            return None
     while _arg_cache and _arg_cache_resident + nbytes > ARG_CACHE_BYTES:
-        _arg_cache_drop(next(iter(_arg_cache)), report)
+        victim = next(k for k in _arg_cache if k != keep)
+        _arg_cache_drop(victim, report)
     try:
         return torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     except Exception:  # noqa: BLE001 - out of HBM: the argument goes uncached
@@ -1076,6 +1111,195 @@ def _patch_packed_args(lib, index, info, total, cache, stage, report):
     return tensors
 
 
+def _rebase_sources(info, cache, base_total):
+    """Check a ``rebase`` entry's ``sources`` against its segments and the
+    held base before anything is handed to the library: one source per
+    segment, each -1 (from the delta) or a multiple of 16 whose rounded
+    segment lies inside the base, and a delta whose layout totals
+    ``rebase_nbytes``.  Returns (base offsets, delta offsets, segments from
+    the delta) or raises ValueError."""
+    sizes = [int(seg["nbytes"]) for seg in info["packed"]]
+    sources = cache["rebase"].get("sources")
+    if not isinstance(sources, (list, tuple)) or len(sources) != len(sizes):
+        raise ValueError("sources do not match the %d segments" % len(sizes))
+    none = (1 << 64) - 1
+    base_offs, delta_offs = [], []
+    delta_bytes = 0
+    from_delta = 0
+    for j, (src, n) in enumerate(zip(sources, sizes)):
+        rounded = (n + 15) // 16 * 16
+        if not isinstance(src, int) or isinstance(src, bool):
+            raise ValueError("source %d is %r" % (j, src))
+        if src == -1:
+            base_offs.append(none)
+            delta_offs.append(delta_bytes)
+            delta_bytes += rounded
+            from_delta += 1
+        elif src >= 0 and src % 16 == 0 and src + rounded <= base_total:
+            base_offs.append(src)
+            delta_offs.append(none)
+        else:
+            raise ValueError(
+                "source %d is %r for %d bytes of a base of %d" % (j, src, n, base_total)
+            )
+    if delta_bytes != int(info["rebase_nbytes"]):
+        raise ValueError(
+            "the delta has %d bytes, its segments need %d"
+            % (int(info["rebase_nbytes"]), delta_bytes)
+        )
+    return base_offs, delta_offs, from_delta
+
+
+def _rebase_packed_args(lib, index, info, total, cache, stage, report):
+    """A ``rebase`` packed entry: the frame is a delta arena, the segments
+    that the held arena ``base`` lacks, in the pack layout.  ONE
+    csp_rebase_unpack_checksum_dev call takes every segment from the base (at
+    the offset ``sources`` names) or from the delta, writes the new arena
+    into a NEW master, scatters it into private tensors and yields its
+    checksum.  The base is only read and stays in the cache under its own
+    key, most recently used but for the new master.  When ARG_CACHE_BYTES
+    cannot hold base and new together there is no new master (a transient
+    rebase): the new key goes to ``not_stored`` and the electron still runs.
+    The frame is consumed whatever happens.  An absent base, another byte
+    count or no ``sum`` is a miss as in _packed_args_from_cache; after a
+    checksum mismatch nobody can tell whether the base or the delta was
+    wrong, so the base goes with the new master and it is a miss.  When the
+    new key is already held the frame is only drained and the tensors come
+    from the arena held under the new key."""
+    global _arg_cache_resident
+    import ctypes
+
+    import torch
+
+    new_key = cache["key"]
+    base_key = cache["rebase"]["base"]
+    delta_total = int(info["rebase_nbytes"])
+    converged = new_key in _arg_cache
+    entry = _arg_cache.get(base_key)
+    reason = None
+    plan = None
+    if converged:
+        pass
+    elif entry is None:
+        reason = "is not in the cache"
+    elif entry[1] != int(cache["rebase"].get("base_nbytes", -1)) or "sum" not in info:
+        reason = "holds %d bytes, the rebase names %r" % (
+            entry[1], cache["rebase"].get("base_nbytes"))
+    else:
+        try:
+            plan = _rebase_sources(info, cache, entry[1])
+        except (ValueError, KeyError, TypeError) as e:
+            reason = "cannot be the base: %s" % e
+    delta = None
+    tensors = None
+    master = None
+    alloc_error = None
+    if reason is None and not converged:
+        try:
+            if delta_total:
+                delta = _alloc_device_arg(
+                    {"shape": [delta_total]}, torch.uint8, report, keep=base_key
+                )
+            tensors = _alloc_packed_tensors(info, report, keep=base_key)
+        except Exception as e:  # noqa: BLE001 - e.g. out of HBM
+            alloc_error = e  # drain mode below: the frame still has to go
+            delta = None
+        if alloc_error is None and base_key in _arg_cache:
+            _arg_cache.move_to_end(base_key)
+            if total:
+                master = _arg_cache_new_master(total, report, keep=base_key)
+    read_ms = ctypes.c_double()
+    h2d_ms = ctypes.c_double()
+    rc = lib.csp_h2d_stream_fd(
+        0, ctypes.c_void_p(delta.data_ptr() if delta is not None else 0),
+        delta_total, _packed_chunk(), -1,
+        ctypes.byref(read_ms), ctypes.byref(h2d_ms),
+    )
+    stage["read_ms"] += read_ms.value
+    stage["h2d_ms"] += h2d_ms.value
+    if rc == 2:
+        # the request stream is no longer aligned: leave, as _receive_device_arg does
+        sys.stderr.write(
+            "csp worker: csp_h2d_stream_fd lost the stream: %s\n"
+            % lib.csp_last_error().decode(errors="replace")
+        )
+        sys.stderr.flush()
+        os._exit(4)
+    if rc == 0:
+        stage["bytes"] += delta_total
+    if converged:
+        return _packed_args_from_cache(lib, index, info, total, new_key, stage, report)
+    if reason is not None:
+        _arg_cache_drop(base_key)
+        report["miss"].append(index)
+        raise RuntimeError(
+            "argument buffer %d: cached argument %s %s" % (index, base_key, reason)
+        )
+    if alloc_error is not None:
+        raise alloc_error
+    if rc != 0:
+        raise RuntimeError(
+            "argument buffer %d: H2D copy failed (rc=%d): %s"
+            % (index, rc, lib.csp_last_error().decode(errors="replace"))
+        )
+    entry = _arg_cache.get(base_key)
+    if entry is None:
+        # the private tensors needed the base's memory (out of HBM)
+        report["miss"].append(index)
+        raise RuntimeError(
+            "argument buffer %d: cached argument %s had to go for the electron's tensors"
+            % (index, base_key)
+        )
+    base_offs, delta_offs, from_delta = plan
+    segs = info["packed"]
+    count = len(segs)
+    sizes = [int(seg["nbytes"]) for seg in segs]
+    dst = (ctypes.c_void_p * count)(
+        *[(t.data_ptr() or None) if n else None for t, n in zip(tensors, sizes)]
+    )
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    rc = lib.csp_rebase_unpack_checksum_dev(
+        ctypes.c_void_p(entry[0].data_ptr() if entry[1] else 0), entry[1],
+        ctypes.c_void_p(delta.data_ptr() if delta is not None else 0), delta_total,
+        ctypes.c_void_p(master.data_ptr() if master is not None else 0), total,
+        dst, (ctypes.c_uint64 * count)(*[int(seg["offset"]) for seg in segs]),
+        (ctypes.c_uint64 * count)(*sizes), (ctypes.c_uint64 * count)(*base_offs),
+        (ctypes.c_uint64 * count)(*delta_offs), count, out, ctypes.byref(kernel_ms),
+    )
+    if rc != 0:
+        raise RuntimeError(
+            "argument buffer %d: csp_rebase_unpack_checksum_dev failed: %s"
+            % (index, lib.csp_last_error().decode(errors="replace"))
+        )
+    got = [int(out[0]), int(out[1])]
+    want = [int(info["sum"][0]), int(info["sum"][1])]
+    if got != want:
+        master = None
+        _arg_cache_drop(base_key)
+        report["miss"].append(index)
+        raise RuntimeError(
+            "argument buffer %d: cached argument %s rebased to %s has checksum %r, "
+            "the dispatcher sent %r" % (index, base_key, new_key, got, want)
+        )
+    if master is not None:
+        _arg_cache[new_key] = (master, total, got)  # most recently used
+        _arg_cache_resident += total
+        report["stored"].append(new_key)
+    else:
+        report["not_stored"].append(new_key)
+    report.setdefault("rebased", []).append([base_key, new_key])
+    stage["mode"] = "pinned-h2d"
+    stage["tensors"] += 1
+    stage["verified"] += 1
+    stage["packed_tensors"] = stage.get("packed_tensors", 0) + count
+    stage["packed_bytes"] = stage.get("packed_bytes", 0) + sum(sizes)
+    stage["rebased_segments"] = stage.get("rebased_segments", 0) + from_delta
+    stage["rebased_bytes"] = stage.get("rebased_bytes", 0) + delta_total
+    stage["rebase_ms"] = round(stage.get("rebase_ms", 0.0) + kernel_ms.value, 3)
+    return tensors
+
+
 def _receive_packed_device_args(index, info, stage, report):
     """Persistent mode: a ``packed`` device entry.  Its one frame lands in
     HBM as one arena through csp_h2d_stream_fd, and ONE
@@ -1087,7 +1311,9 @@ def _receive_packed_device_args(index, info, stage, report):
     frame and the tensors are unpacked from the master already held
     (_packed_args_from_cache); with ``{"key", "patch": {"base", "segments"}}``
     the frame is a delta that is applied to the master held under ``base``
-    (_patch_packed_args).  A transient arena is let go before user code
+    (_patch_packed_args); with ``{"key", "rebase": {"base", "base_nbytes",
+    "sources"}}`` the frame is a delta from which, with the master held under
+    ``base``, a new master is built (_rebase_packed_args).  A transient arena is let go before user code
     runs.  Whatever goes wrong short of a broken stream, the frame is
     consumed before the error is raised, as in _receive_device_arg."""
     global _arg_cache_resident
@@ -1111,6 +1337,8 @@ def _receive_packed_device_args(index, info, stage, report):
         )
     if cache.get("patch"):
         return _patch_packed_args(lib, index, info, total, cache, stage, report)
+    if cache.get("rebase"):
+        return _rebase_packed_args(lib, index, info, total, cache, stage, report)
     key = None
     master = None
     if cache.get("store") and "sum" in info and total:

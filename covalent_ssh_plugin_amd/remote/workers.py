@@ -44,7 +44,8 @@ class WorkerHandle:
     #: for the packed arenas among them that were sent with
     #: ``patch_tensor_args`` on: key -> ``((segment_key, nbytes), ...)``, what
     #: a later arena of the same layout is compared with to send a delta.
-    #: Maintained wherever ``resident`` is.
+    #: Maintained wherever ``resident`` is.  With ``rebase_tensor_args`` in
+    #: order of use, the most recently stored or used arena last.
     resident_arenas: Dict[str, tuple] = field(default_factory=dict)
 
     @property
@@ -232,6 +233,9 @@ PACK_ALIGN = 16  # csp_pack_dev's layout rule: every segment starts on a multipl
 # stays far below 2^32, where the checksum's weight wraps, so
 # compose_packed_checksum is exact.  A condition, not a measurement.
 PACK_ARGS_MAX_BYTES = 4 << 30
+#: rebase_tensor_args: how many of the most recently used resident arenas are
+#: compared with a new one (bounds the planning cost; not a measurement)
+REBASE_CANDIDATES = 8
 
 
 def compose_packed_checksum(sums, offsets):
@@ -275,7 +279,7 @@ def packed_content_key(segment_keys) -> str:
 
 
 def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
-                     buffers, buffer_meta, patch_max_fraction=None):
+                     buffers, buffer_meta, patch_max_fraction=None, rebase=False):
     """The ``pack_tensor_args`` half of :func:`extract_arg_buffers`: emit the
     packed entry when the rule in its docstring holds.  Returns
     ``{id(tensor): marker}``, empty when nothing is packed.  Only called with
@@ -286,7 +290,8 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
     rebuilds ``"cache"`` for the wire), ``"segments"``: the per-segment
     ``(content key, nbytes)``, ``"seg_parts"``: per segment its parts of the
     frame (the tensor's own memory and its zero padding), and the
-    fraction."""
+    fraction; with ``rebase`` (``rebase_tensor_args``) also ``"rebase":
+    True``."""
     import ctypes
 
     import torch
@@ -363,6 +368,8 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
                     segments=segment_keys, seg_parts=seg_parts,
                     patch_max_fraction=float(patch_max_fraction),
                 )
+                if rebase:
+                    info["cache"]["rebase"] = True
     # the source tensors stay alive until the frame is drained
     buffers.append((FrameParts(parts), srcs))
     buffer_meta.append(info)
@@ -377,6 +384,7 @@ def extract_arg_buffers(
     cache_min_bytes: Optional[int] = None,
     pack_min_bytes: Optional[int] = None,
     patch_max_fraction: Optional[float] = None,
+    rebase: bool = False,
 ):
     """Pull large contiguous CPU torch tensors out of (args, kwargs) and
     replace them with out-of-band buffer markers (the request-direction
@@ -422,7 +430,12 @@ def extract_arg_buffers(
     keeps its per-segment keys and parts on the dispatcher side, so that
     :func:`run_task` can send it as a delta against an arena of the same
     layout that the worker holds (:class:`_ArgCacheSend`).  Nothing of it
-    reaches the wire."""
+    reaches the wire.
+
+    ``rebase`` (the executor's ``rebase_tensor_args``, with
+    ``patch_max_fraction``): such an entry is instead planned against ANY
+    arena the worker holds, whatever its layout, and built there as a new
+    master that leaves the base in the cache (:meth:`_ArgCacheSend._plan_rebase`)."""
     import sys
 
     if "torch" not in sys.modules:
@@ -437,7 +450,7 @@ def extract_arg_buffers(
     if to_device and pack_min_bytes is not None:
         packed_markers = _pack_small_args(
             args, kwargs, threshold, cache_min_bytes, pack_min_bytes, buffers, buffer_meta,
-            patch_max_fraction=patch_max_fraction,
+            patch_max_fraction=patch_max_fraction, rebase=rebase,
         )
 
     def extract(t):
@@ -604,6 +617,10 @@ class _ArgCacheSend:
         #: per entry ``(base key, changed segment indices, delta FrameParts)``
         #: when the last :meth:`frames` sent it as a patch, else None
         self.patches = [None] * len(entries)
+        #: per entry ``(base key, base arena bytes, per-segment base offset or
+        #: -1, delta FrameParts)`` when the last :meth:`frames` sent it as a
+        #: rebase, else None
+        self.rebases = [None] * len(entries)
 
     def _plan_patch(self, cache):
         """``patch_tensor_args``: the delta that turns an arena the worker
@@ -633,12 +650,61 @@ class _ArgCacheSend:
         delta = FrameParts([p for j in changed for p in cache["seg_parts"][j]])
         return base, changed, delta
 
+    def _plan_rebase(self, cache):
+        """``rebase_tensor_args``: the held arena and the delta that this
+        arena is built from on the worker, or None.  Candidates are the
+        resident arenas, the :data:`REBASE_CANDIDATES` most recently stored
+        or used (a bound on the planning cost, not a measurement).  A segment
+        is reusable when the candidate holds one with the same ``(content
+        key, nbytes)``, wherever it lies; duplicates share one source.  The
+        candidate that leaves the fewest rounded delta bytes wins, a tie goes
+        to the most recent; a rebase only when they are more than none and at
+        most ``patch_max_fraction`` of the arena."""
+        segments = cache["segments"]
+        arenas = self.handle.resident_arenas
+        recent = [k for k in reversed(list(arenas)) if k in self.handle.resident]
+        best = None
+        for base in recent[:REBASE_CANDIDATES]:
+            where = {}
+            offset = 0
+            for seg in arenas[base]:
+                where.setdefault(tuple(seg), offset)
+                offset += -(-seg[1] // PACK_ALIGN) * PACK_ALIGN
+            sources = [where.get(tuple(seg), -1) for seg in segments]
+            nbytes = sum(
+                -(-seg[1] // PACK_ALIGN) * PACK_ALIGN
+                for seg, src in zip(segments, sources) if src < 0
+            )
+            if best is None or nbytes < best[0]:
+                best = (nbytes, base, offset, sources)
+        if best is None:
+            return None
+        nbytes, base, base_nbytes, sources = best
+        total = sum(-(-n // PACK_ALIGN) * PACK_ALIGN for _key, n in segments)
+        if not 0 < nbytes <= cache["patch_max_fraction"] * total:
+            return None
+        # cut from the tensors' own memory and the zero padding: no host copy
+        delta = FrameParts(
+            [p for j, src in enumerate(sources) if src < 0 for p in cache["seg_parts"][j]]
+        )
+        return base, base_nbytes, sources, delta
+
+    def _touch(self, key):
+        """``rebase_tensor_args``: ``key`` was used, so it is the most recent
+        of ``resident_arenas``."""
+        arenas = self.handle.resident_arenas
+        if key in arenas:
+            arenas[key] = arenas.pop(key)
+
     def _now_resident(self, index, key):
         """``key``'s frame has been written: the worker holds it from here on
         as far as later requests on this channel are concerned."""
         self.handle.resident.add(key)
-        segments = (self.entries[index].get("cache") or {}).get("segments")
+        cache = self.entries[index].get("cache") or {}
+        segments = cache.get("segments")
         if segments is not None:
+            if cache.get("rebase"):
+                self.handle.resident_arenas.pop(key, None)  # most recent: last
             self.handle.resident_arenas[key] = segments
 
     def _forget(self, key):
@@ -655,15 +721,29 @@ class _ArgCacheSend:
             key is not None and not full and key in resident for key in self.keys
         ]
         self.patches = [None] * len(self.entries)
+        self.rebases = [None] * len(self.entries)
         wire = []
         for index, (info, key, ref) in enumerate(zip(self.entries, self.keys, self.refs)):
             if key is not None:
                 cache = info["cache"]
                 info = dict(info)
+                if ref and cache.get("rebase"):
+                    self._touch(key)
                 if not ref and not full and cache.get("segments") is not None:
-                    self.patches[index] = self._plan_patch(cache)
+                    if cache.get("rebase"):
+                        self.rebases[index] = self._plan_rebase(cache)
+                    else:
+                        self.patches[index] = self._plan_patch(cache)
                 patch = self.patches[index]
-                if patch is not None:
+                rebase = self.rebases[index]
+                if rebase is not None:
+                    info["cache"] = {
+                        "key": key,
+                        "rebase": {"base": rebase[0], "base_nbytes": rebase[1],
+                                   "sources": rebase[2]},
+                    }
+                    info["rebase_nbytes"] = rebase[3].nbytes
+                elif patch is not None:
                     info["cache"] = {
                         "key": key, "patch": {"base": patch[0], "segments": patch[1]},
                     }
@@ -676,7 +756,12 @@ class _ArgCacheSend:
             if ref:
                 continue
             patch = self.patches[index]
-            yield view if patch is None else patch[2]
+            rebase = self.rebases[index]
+            if rebase is not None:
+                yield rebase[3]
+                self._touch(rebase[0])  # the base stays, and was used
+            else:
+                yield view if patch is None else patch[2]
             if patch is not None:
                 self._forget(patch[0])  # patched in place: the base is gone
             if key is not None:
@@ -696,6 +781,9 @@ class _ArgCacheSend:
             if self.patches[i] is not None:
                 # a failed patch in place: the worker let the base go
                 self._forget(self.patches[i][0])
+            if self.rebases[i] is not None:
+                # nobody can tell whether the base or the delta was wrong
+                self._forget(self.rebases[i][0])
         done = {tuple(pair) for pair in (report.get("patched") or ())}
         stats = self.cache_stats
         if stats is not None:
@@ -705,6 +793,14 @@ class _ArgCacheSend:
                     stats["arg_cache_bytes_saved"] = (
                         stats.get("arg_cache_bytes_saved", 0)
                         + _view_nbytes(view) - patch[2].nbytes
+                    )
+            rebased = {tuple(pair) for pair in (report.get("rebased") or ())}
+            for view, key, rebase in zip(self.views, self.keys, self.rebases):
+                if rebase is not None and (rebase[0], key) in rebased:
+                    stats["arg_cache_rebases"] = stats.get("arg_cache_rebases", 0) + 1
+                    stats["arg_cache_bytes_saved"] = (
+                        stats.get("arg_cache_bytes_saved", 0)
+                        + _view_nbytes(view) - rebase[3].nbytes
                     )
             for view, key, ref in zip(self.views, self.keys, self.refs):
                 if ref and key in held:
@@ -761,6 +857,15 @@ async def run_task(
     the resend never patches.  ``cache_stats`` also gets
     ``arg_cache_patches``, and ``arg_cache_bytes_saved`` grows by the arena
     bytes that the delta left out.
+
+    With ``rebase_tensor_args`` such an entry is instead compared with the
+    most recently used resident arenas of ANY layout
+    (:meth:`_ArgCacheSend._plan_rebase`) and travels as ``{"key", "rebase":
+    {"base", "base_nbytes", "sources"}}`` with a frame of only the segments
+    the base lacks.  The worker builds a new master and keeps the base, so
+    once that frame has been written both keys are resident.  A miss on a
+    rebase forgets both; the new key in ``not_stored`` forgets it alone; the
+    resend never rebases.  ``cache_stats`` gets ``arg_cache_rebases``.
     """
     entries = arg_buffer_meta or []
     cache = None

@@ -163,6 +163,14 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # measurement: a patch always sends fewer bytes than a store, but it
     # consumes the base, which a store would have left in the cache.
     "patch_args_max_fraction": 0.5,
+    # With patch_tensor_args: a packed argument arena whose key the worker
+    # does not hold is built on the worker as a NEW master from any held
+    # arena plus a delta of the tensors that arena lacks, whatever the two
+    # layouts (a tensor added, removed or resized), in the same kernel launch
+    # that scatters and verifies it.  The base stays cached under its own
+    # key, so alternating between states costs a delta once and hits after.
+    # Replaces the in-place patch; bounded by patch_args_max_fraction.
+    "rebase_tensor_args": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -363,6 +371,7 @@ class SSHExecutor(RemoteExecutor):
         pack_args_min_bytes: Optional[int] = None,
         patch_tensor_args: Optional[bool] = None,
         patch_args_max_fraction: Optional[float] = None,
+        rebase_tensor_args: Optional[bool] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -487,6 +496,15 @@ class SSHExecutor(RemoteExecutor):
         )
         if not 0.0 < self.patch_args_max_fraction <= 1.0:
             raise ValueError("patch_args_max_fraction must be in (0, 1]")
+        self.rebase_tensor_args = bool(
+            _conf("rebase_tensor_args", rebase_tensor_args, default=False)
+        )
+        if self.rebase_tensor_args and not self.patch_tensor_args:
+            raise ValueError(
+                "rebase_tensor_args needs patch_tensor_args=True: it builds a "
+                "packed argument arena from one that the worker holds in its "
+                "cache plus a delta"
+            )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -531,6 +549,9 @@ class SSHExecutor(RemoteExecutor):
             # patch_tensor_args: packed arenas sent as a delta against an
             # arena the worker held (the bytes left out count as saved)
             "arg_cache_patches": 0,
+            # rebase_tensor_args: packed arenas built on the worker from a
+            # held arena plus a delta (the bytes left out count as saved)
+            "arg_cache_rebases": 0,
         }
 
     # ------------------------------------------------------------------
@@ -1372,6 +1393,7 @@ class SSHExecutor(RemoteExecutor):
                                 if self.patch_tensor_args
                                 else None
                             ),
+                            **({"rebase": True} if self.rebase_tensor_args else {}),
                         )
                     )
                     function_blob = cloudpickle.dumps((function, s_args, s_kwargs))
