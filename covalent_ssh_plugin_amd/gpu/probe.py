@@ -13,6 +13,8 @@ gfx950 only) provides:
 * ``csp_checksum_dev`` — the argument checksum over bytes in HBM,
 * ``csp_pack_dev`` — many small device buffers gathered into one contiguous
   zero-padded arena by one kernel launch (``pack_tensor_results``),
+* ``csp_pack_checksum_dev`` — the same gather with the arena's checksum from
+  the same launch (``retain_tensor_results``),
 * ``csp_unpack_checksum_dev`` — such an arena scattered into private
   per-tensor buffers and checksummed by one kernel launch
   (``pack_tensor_args``),
@@ -149,6 +151,19 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_pack_tile_bytes.restype = ctypes.c_size_t
     lib.csp_pack_tile_bytes.argtypes = []
+    lib.csp_pack_checksum_dev.restype = ctypes.c_int
+    lib.csp_pack_checksum_dev.argtypes = [
+        ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_pack_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_pack_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_unpack_checksum_dev.restype = ctypes.c_int
     lib.csp_unpack_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -418,6 +433,40 @@ def pack_device(segments, arena_ptr: int, arena_bytes: int) -> dict:
         "csp_pack_dev",
     )
     return {"kernel_ms": kernel_ms.value}
+
+
+def pack_checksum_device(segments, arena_ptr: int, arena_bytes: int) -> dict:
+    """:func:`pack_device` and :func:`checksum_device` of the arena in ONE
+    kernel launch (``retain_tensor_results``): every 16-byte vector is
+    assembled once, stored once and summed as stored.  One segment is a
+    checksummed copy from a source of any alignment.  Refuses what
+    :func:`pack_device` refuses and also an ``arena_bytes`` above 16 GiB and a
+    source range that overlaps the arena (``GpuLibError``, nothing launched).
+    Returns ``{"sum": (s0, s1), "kernel_ms": ...}``, the kernel alone.  Runs
+    on the library's copy stream; sources written on another stream must be
+    complete (``torch.cuda.synchronize()``) first."""
+    lib = load()
+    n = len(segments)
+    src = (ctypes.c_void_p * n)(*[int(s[0]) or None for s in segments])
+    off = (ctypes.c_uint64 * n)(*[int(s[1]) for s in segments])
+    size = (ctypes.c_uint64 * n)(*[int(s[2]) for s in segments])
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_pack_checksum_dev(
+            src, off, size, n, ctypes.c_void_p(arena_ptr or None), arena_bytes, out,
+            ctypes.byref(kernel_ms),
+        ),
+        "csp_pack_checksum_dev",
+    )
+    return {"sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
+
+
+def pack_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`pack_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_pack_checksum_grid_cap(int(cap)))
 
 
 def unpack_checksum_device(arena_ptr: int, arena_bytes: int, segments) -> dict:

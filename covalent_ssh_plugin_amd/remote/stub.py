@@ -71,6 +71,7 @@ def render_worker(
     pack_results: bool = False,
     pack_min_bytes: int = 0,
     arg_cache_bytes: int = 0,
+    retain_min_bytes: Optional[int] = None,
 ) -> str:
     """Return the persistent worker script text (one per endpoint; the
     GPU slot arrives via the CSP_GPU_SLOT env var at launch).  With
@@ -80,7 +81,10 @@ def render_worker(
     makes the worker send the small CUDA tensors of a result as one packed
     frame when they total at least ``pack_min_bytes``.  ``arg_cache_bytes``
     is the worker's budget for repeated tensor arguments kept in HBM
-    (``cache_tensor_args``); 0 means no cache."""
+    (``cache_tensor_args``); 0 means no cache.  ``retain_min_bytes``
+    (``retain_tensor_results``; ``None`` is off) is the executor's
+    ``arg_cache_min_bytes``: the worker keeps CUDA result buffers as argument
+    masters in that cache, split where the argument side splits them."""
     text = _template_text(str(_WORKER_TEMPLATE_PATH))
     thr = DEFAULT_STAGING_THRESHOLD if staging_threshold is None else int(staging_threshold)
     replacements = {
@@ -95,6 +99,7 @@ def render_worker(
         "__CSP_PACK_RESULTS__": repr(bool(pack_results)),
         "__CSP_PACK_MIN_BYTES__": str(int(pack_min_bytes)),
         "__CSP_ARG_CACHE_BYTES__": str(int(arg_cache_bytes)),
+        "__CSP_RETAIN_MIN_BYTES__": str(-1 if retain_min_bytes is None else int(retain_min_bytes)),
     }
     for token, value in replacements.items():
         text = text.replace(token, value)

@@ -93,8 +93,23 @@ Protocol (all frames: 8-byte big-endian length + payload):
              ("__csp_packed_tensor_v1__", i, j), and meta["buffers"][i] is
              {"packed": [{dtype, shape, offset, nbytes}, ...], "nbytes",
              "sum": [s0, s1]} with csp_checksum_dev's checksum of the arena,
-             which the dispatcher verifies.  A zero-length request frame
-             means: shut down.
+             which the dispatcher verifies.  With the executor option
+             retain_tensor_results the worker keeps CUDA result buffers in
+             HBM as argument masters of the cache above: a CUDA tensor of at
+             least min(STAGING_THRESHOLD, arg_cache_min_bytes) bytes is its
+             own buffer, smaller ones share the packed arena, and for each
+             ONE csp_pack_checksum_dev call gathers it into a new master
+             (within ARG_CACHE_BYTES) and yields its checksum; the frame is
+             streamed from the master, which stays under the worker's name
+             "r:<op_id>:<buffer index>".  meta["buffers"][i] then carries
+             "sum" and "retained": name, and meta["retained"] is {"stored",
+             "not_stored", "evicted"} (every key retention pushed out).  The
+             dispatcher later names such a master wherever a request refers
+             to something held: the key of a "ref", the base of a "patch" or
+             a "rebase" (whose delta may then be empty).  A buffer that
+             cannot be retained takes the path above and
+             meta["staging"]["retain_fallback"] says why.  A zero-length
+             request frame means: shut down.
 
 The worker's REAL stdout is reserved for the protocol; fd 1 is
 re-pointed at stderr before any user code runs, so user prints cannot
@@ -123,6 +138,10 @@ PACK_MIN_BYTES = int(__CSP_PACK_MIN_BYTES__)
 # Budget in bytes for the masters of repeated tensor arguments kept in HBM
 # (executor option cache_tensor_args); 0 = no cache.
 ARG_CACHE_BYTES = int(__CSP_ARG_CACHE_BYTES__)
+# Keep CUDA result buffers as argument masters in that cache (executor option
+# retain_tensor_results): the executor's arg_cache_min_bytes, so that results
+# are split into buffers where the argument side splits them; -1 = off.
+RETAIN_MIN_BYTES = int(__CSP_RETAIN_MIN_BYTES__)
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
 # break the children) and every electron executes in a freshly forked
@@ -276,6 +295,18 @@ def _load_gpu_lib():
         ctypes.POINTER(ctypes.c_uint64),
         ctypes.POINTER(ctypes.c_double),
     ]
+    if RETAIN_MIN_BYTES >= 0:
+        lib.csp_pack_checksum_dev.restype = ctypes.c_int
+        lib.csp_pack_checksum_dev.argtypes = [
+            ctypes.POINTER(ctypes.c_void_p),
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.c_size_t,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_double),
+        ]
     lib.csp_patch_unpack_checksum_dev.restype = ctypes.c_int
     lib.csp_patch_unpack_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -391,16 +422,117 @@ def _send_buffer(fd, view):
         os._exit(4)
 
 
-def _small_cuda_tensors(result):
-    """The CUDA tensors of ``result`` below STAGING_THRESHOLD, each object
-    once, in walk order."""
+def _retain_large_bytes():
+    """With retention on, a CUDA result tensor of at least this many bytes is
+    its own out-of-band buffer: where the argument side stops packing."""
+    return min(STAGING_THRESHOLD, RETAIN_MIN_BYTES)
+
+
+def _pack_checksum(lib, src_ptrs, offsets, sizes, arena_ptr, total):
+    """One csp_pack_checksum_dev call; returns [s0, s1] of the arena."""
+    import ctypes
+
+    count = len(sizes)
+    out = (ctypes.c_uint64 * 2)()
+    rc = lib.csp_pack_checksum_dev(
+        (ctypes.c_void_p * count)(*src_ptrs), (ctypes.c_uint64 * count)(*offsets),
+        (ctypes.c_uint64 * count)(*sizes), count, ctypes.c_void_p(arena_ptr), total,
+        out, None,
+    )
+    if rc != 0:
+        raise RuntimeError(
+            "csp_pack_checksum_dev failed (rc=%d): %s"
+            % (rc, lib.csp_last_error().decode(errors="replace"))
+        )
+    return [int(out[0]), int(out[1])]
+
+
+def _retain_buffer(lib, retain, index, src_ptrs, offsets, sizes, total, nbytes, stats,
+                   keep=True):
+    """Result buffer ``index`` gathered, copied and checksummed by one
+    csp_pack_checksum_dev call into a buffer of its own of ``total`` bytes,
+    which with ``keep`` is a new argument master held under the worker's name
+    "r:<op_id>:<index>" as (master, nbytes, sum).  Returns (buffer, sum,
+    name or None).  No room in the budget, no HBM, or any refusal or error of
+    the call: None, the reason in stats["retain_fallback"], and the buffer
+    takes the path it takes without retention.  The caller has synchronised
+    the null stream."""
+    global _arg_cache_resident
+    import torch
+
+    t0 = time.monotonic()
+    report = retain["report"]
+    name = "r:%s:%d" % (retain["op_id"], index) if keep else None
+    evicted = _new_arg_cache_report()
+    try:
+        if keep:
+            _arg_cache_drop(name)  # an op_id used twice: the new result replaces the old
+            arena = _arg_cache_new_master(total, evicted)
+            if arena is None:
+                raise RuntimeError(
+                    "no room for %d bytes in the budget of %d or in HBM"
+                    % (total, ARG_CACHE_BYTES)
+                )
+        else:
+            arena = torch.empty(total, dtype=torch.uint8, device="cuda")
+        sums = _pack_checksum(lib, src_ptrs, offsets, sizes, arena.data_ptr(), total)
+    except Exception as e:  # noqa: BLE001 - retention never fails a task
+        stats["retain_fallback"] = repr(e)[:500]
+        if keep:
+            report["not_stored"].append(name)
+        return None
+    finally:
+        report["evicted"].extend(evicted["evicted"])
+        stats["retain_ms"] = round(
+            stats.get("retain_ms", 0.0) + (time.monotonic() - t0) * 1000, 3
+        )
+    if keep:
+        _arg_cache[name] = (arena, nbytes, sums)
+        _arg_cache_resident += total  # as allocated and as checked against the budget
+        report["stored"].append(name)
+        retain.setdefault("sizes", {})[name] = nbytes
+        stats["retained_buffers"] = stats.get("retained_buffers", 0) + 1
+        stats["retained_bytes"] = stats.get("retained_bytes", 0) + nbytes
+    return arena, sums, name
+
+
+def _retain_settle(retain, buffer_meta, stats):
+    """After staging: a master that a later buffer of the same result pushed
+    out of the budget is not held after all."""
+    report = retain["report"]
+    gone = [name for name in report["stored"] if name not in _arg_cache]
+    for name in gone:
+        report["stored"].remove(name)
+        report["not_stored"].append(name)
+        stats["retained_buffers"] -= 1
+        stats["retained_bytes"] -= retain["sizes"][name]
+        for info in buffer_meta:
+            if info.get("retained") == name:
+                del info["retained"]
+    report["evicted"] = [k for k in report["evicted"] if k not in gone]
+
+
+def _retain_rollback(retain):
+    """The result does not leave after all: nothing of it stays held."""
+    report = retain["report"]
+    for name in report["stored"]:
+        _arg_cache_drop(name)
+    report["not_stored"].extend(report["stored"])
+    report["stored"] = []
+
+
+def _small_cuda_tensors(result, limit=None):
+    """The CUDA tensors of ``result`` below ``limit`` (STAGING_THRESHOLD when
+    None), each object once, in walk order."""
     import torch
 
     found = {}
+    if limit is None:
+        limit = STAGING_THRESHOLD
 
     def walk(obj):
         if isinstance(obj, torch.Tensor):
-            if obj.is_cuda and obj.numel() * obj.element_size() < STAGING_THRESHOLD:
+            if obj.is_cuda and obj.numel() * obj.element_size() < limit:
                 found.setdefault(id(obj), obj)
         elif isinstance(obj, dict):
             for v in obj.values():
@@ -413,7 +545,7 @@ def _small_cuda_tensors(result):
     return list(found.values())
 
 
-def _pack_small_cuda(lib, result, stats, buffers, buffer_meta):
+def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
     """Gather the small CUDA tensors of ``result`` into one device arena
     with csp_pack_dev and emit it as one streamed buffer.  Returns
     {id(tensor): marker}; empty when there is nothing to pack, the total is
@@ -421,15 +553,24 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta):
     stats["pack_fallback"] and the tensors take the per-tensor path).
 
     The arena is a transient second copy of the packed tensors in HBM until
-    its frame is sent; only the out-of-memory fallback bounds its size."""
+    its frame is sent; only the out-of-memory fallback bounds its size.
+
+    With ``retain`` (retention on) the small tensors are those below
+    _retain_large_bytes(), one csp_pack_checksum_dev call stands in for
+    csp_pack_dev and csp_checksum_dev, and an arena of at least
+    max(1, RETAIN_MIN_BYTES) bytes stays in HBM as an argument master
+    (_retain_buffer); when that fails the two calls run as without it."""
     import ctypes
 
     import torch
 
-    tensors = _small_cuda_tensors(result)
+    tensors = _small_cuda_tensors(
+        result, None if retain is None else _retain_large_bytes()
+    )
     sizes = [t.numel() * t.element_size() for t in tensors]
     if not tensors or sum(sizes) == 0 or sum(sizes) < PACK_MIN_BYTES:
         return {}
+    name = None
     try:
         # torch makes non-contiguous tensors contiguous, as on the large path
         srcs = [t.contiguous() for t in tensors]
@@ -440,28 +581,35 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta):
             total += (n + 15) // 16 * 16
         # the library's copy stream does not wait on the null stream
         torch.cuda.synchronize()
-        arena = torch.empty(total, dtype=torch.uint8, device="cuda")
         count = len(srcs)
-        src_ptrs = (ctypes.c_void_p * count)(
-            *[(t.data_ptr() or None) if n else None for t, n in zip(srcs, sizes)]
-        )
-        rc = lib.csp_pack_dev(
-            src_ptrs, (ctypes.c_uint64 * count)(*offsets),
-            (ctypes.c_uint64 * count)(*sizes), count,
-            ctypes.c_void_p(arena.data_ptr()), total, None,
-        )
-        if rc != 0:
-            raise RuntimeError(
-                "csp_pack_dev failed (rc=%d): %s"
-                % (rc, lib.csp_last_error().decode(errors="replace"))
+        ptrs = [(t.data_ptr() or None) if n else None for t, n in zip(srcs, sizes)]
+        kept = None
+        if retain is not None:
+            kept = _retain_buffer(
+                lib, retain, len(buffers), ptrs, offsets, sizes, total, total, stats,
+                keep=total >= max(1, RETAIN_MIN_BYTES),
             )
-        sums = (ctypes.c_uint64 * 2)()
-        rc = lib.csp_checksum_dev(ctypes.c_void_p(arena.data_ptr()), total, sums)
-        if rc != 0:
-            raise RuntimeError(
-                "csp_checksum_dev failed (rc=%d): %s"
-                % (rc, lib.csp_last_error().decode(errors="replace"))
+        if kept is not None:
+            arena, sums, name = kept
+        else:
+            arena = torch.empty(total, dtype=torch.uint8, device="cuda")
+            rc = lib.csp_pack_dev(
+                (ctypes.c_void_p * count)(*ptrs), (ctypes.c_uint64 * count)(*offsets),
+                (ctypes.c_uint64 * count)(*sizes), count,
+                ctypes.c_void_p(arena.data_ptr()), total, None,
             )
+            if rc != 0:
+                raise RuntimeError(
+                    "csp_pack_dev failed (rc=%d): %s"
+                    % (rc, lib.csp_last_error().decode(errors="replace"))
+                )
+            sums = (ctypes.c_uint64 * 2)()
+            rc = lib.csp_checksum_dev(ctypes.c_void_p(arena.data_ptr()), total, sums)
+            if rc != 0:
+                raise RuntimeError(
+                    "csp_checksum_dev failed (rc=%d): %s"
+                    % (rc, lib.csp_last_error().decode(errors="replace"))
+                )
     except Exception as e:  # noqa: BLE001 - packing never fails a task
         stats["pack_fallback"] = repr(e)[:500]
         return {}
@@ -476,6 +624,8 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta):
         "nbytes": total,
         "sum": [int(sums[0]), int(sums[1])],
     })
+    if name is not None:
+        buffer_meta[-1]["retained"] = name
     index = len(buffers) - 1
     stats["packed_tensors"] = count
     stats["packed_bytes"] = sum(sizes)
@@ -485,14 +635,21 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta):
     }
 
 
-def _stage_result(result, stats, buffers, buffer_meta):
+def _stage_result(result, stats, buffers, buffer_meta, retain=None):
     """Replace large tensors in ``result`` with out-of-band buffer
     markers.  A large CUDA tensor is only recorded here (device pointer,
     byte count, the tensor as keep-alive); the send loop streams it
     through hipHostMalloc-pinned memory.  Large contiguous CPU tensors
     are shipped zero-copy from their own storage.  Small tensors stay
     inline in the pickle, unless PACK_RESULTS gathers the small CUDA
-    tensors into one more streamed buffer (_pack_small_cuda)."""
+    tensors into one more streamed buffer (_pack_small_cuda).
+
+    ``retain`` ({"op_id", "report"}; retention on): a CUDA tensor of at least
+    _retain_large_bytes() bytes is copied and checksummed by one
+    csp_pack_checksum_dev call into a new argument master, its frame is
+    streamed from the master (the user's tensor is let go) and its meta entry
+    carries "sum" and "retained"; the packed arena likewise.  A buffer that
+    cannot be retained takes the path it takes without retention."""
     if "torch" not in sys.modules:
         return result
     import ctypes
@@ -506,9 +663,11 @@ def _stage_result(result, stats, buffers, buffer_meta):
         except Exception:  # noqa: BLE001
             lib = None
 
+    if lib is None:
+        retain = None
     packed = {}
     if PACK_RESULTS and lib is not None:
-        packed = _pack_small_cuda(lib, result, stats, buffers, buffer_meta)
+        packed = _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain)
 
     def emit_buffer(view, keepalive, dtype, shape):
         buffers.append((view, keepalive))
@@ -517,12 +676,43 @@ def _stage_result(result, stats, buffers, buffer_meta):
         )
         return ("__csp_tensor_buffer_v1__", len(buffers) - 1)
 
+    retained_markers = {}  # id(tensor) -> marker: one object met twice, one master
+
+    def retain_large(t, nbytes):
+        """The marker of ``t``'s retained buffer, or None."""
+        if id(t) in retained_markers:
+            return retained_markers[id(t)]
+        src_t = t.contiguous()
+        # the library's copy stream does not wait on the null stream
+        torch.cuda.synchronize()
+        total = (nbytes + 15) // 16 * 16
+        kept = _retain_buffer(
+            lib, retain, len(buffers), [src_t.data_ptr()], [0], [nbytes], total, nbytes,
+            stats,
+        )
+        if kept is None:
+            return None
+        master, sums, name = kept
+        stats["pinned_tensors"] += 1
+        stats["mode"] = "pinned"
+        marker = emit_buffer(
+            _DeferredCuda(lib, master.data_ptr(), nbytes), master, src_t.dtype, src_t.shape
+        )
+        buffer_meta[-1]["sum"] = sums
+        buffer_meta[-1]["retained"] = name
+        retained_markers[id(t)] = marker
+        return marker
+
     def to_host(t):
         stats["tensors"] += 1
         nbytes = t.numel() * t.element_size()
         stats["bytes"] += nbytes
         if id(t) in packed:
             return packed[id(t)]
+        if retain is not None and t.is_cuda and 0 < nbytes >= _retain_large_bytes():
+            marker = retain_large(t, nbytes)
+            if marker is not None:
+                return marker
         if nbytes < STAGING_THRESHOLD:
             return t.cpu() if t.is_cuda else t
         if t.is_cuda:
@@ -557,7 +747,10 @@ def _stage_result(result, stats, buffers, buffer_meta):
             return [walk(v) for v in obj]
         return obj
 
-    return walk(result)
+    staged = walk(result)
+    if retain is not None:
+        _retain_settle(retain, buffer_meta, stats)
+    return staged
 
 
 def _read_frame(fd, idle_timeout=0.0):
@@ -682,7 +875,9 @@ def _arg_cache_drop(key, report=None):
     global _arg_cache_resident
     entry = _arg_cache.pop(key, None)
     if entry is not None:
-        _arg_cache_resident -= entry[1]
+        # what the master holds: nbytes, or for a retained large result the
+        # next multiple of 16
+        _arg_cache_resident -= entry[0].numel()
         if report is not None:
             report["evicted"].append(key)
 
@@ -1557,6 +1752,7 @@ def _serve_one(request):
     result = None
     exception = None
     buffers = []
+    retain = None  # retention on and a result to stage: {"op_id", "report"}
     try:
         if request.get("_arg_error") is not None:
             # an argument frame was consumed but could not be delivered:
@@ -1612,12 +1808,19 @@ def _serve_one(request):
         if PACK_RESULTS:
             stats["packed_tensors"] = 0
             stats["packed_bytes"] = 0
+        if RETAIN_MIN_BYTES >= 0 and ARG_CACHE_BYTES > 0 and not ISOLATE:
+            retain = {"op_id": request.get("op_id"),
+                      "report": {"stored": [], "not_stored": [], "evicted": []}}
+            stats.update(retained_buffers=0, retained_bytes=0, retain_ms=0.0)
+            meta["retained"] = retain["report"]
         try:
-            result = _stage_result(result, stats, buffers, meta["buffers"])
+            result = _stage_result(result, stats, buffers, meta["buffers"], retain)
             meta["staging"] = stats
         except Exception as e:  # noqa: BLE001
             result, exception, buffers = None, e, []
             meta["buffers"] = []
+            if retain is not None:
+                _retain_rollback(retain)
         meta["phases_ms"]["staging"] = round((time.monotonic() - t_stage) * 1000, 3)
 
     try:
@@ -1626,6 +1829,8 @@ def _serve_one(request):
         result_blob = pickle.dumps((None, e))
         buffers = []
         meta["buffers"] = []
+        if retain is not None:
+            _retain_rollback(retain)
     meta["phases_ms"]["total"] = round((time.monotonic() - t0) * 1000, 3)
     return result_blob, meta, buffers
 

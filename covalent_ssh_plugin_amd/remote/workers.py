@@ -47,6 +47,15 @@ class WorkerHandle:
     #: Maintained wherever ``resident`` is.  With ``rebase_tensor_args`` in
     #: order of use, the most recently stored or used arena last.
     resident_arenas: Dict[str, tuple] = field(default_factory=dict)
+    #: ``retain_tensor_results``: the worker's names ("r:<op_id>:<index>") of
+    #: the result buffers it is believed to hold as argument masters
+    retained: Set[str] = field(default_factory=set)
+    #: content key -> worker name, for the retained buffers whose bytes have
+    #: been keyed: what the wire carries in place of the key
+    names: Dict[str, str] = field(default_factory=dict)
+    #: keying of retained buffers still running in the background; joined
+    #: before a request to this worker is planned
+    keying: list = field(default_factory=list)
 
     @property
     def alive(self) -> bool:
@@ -208,7 +217,7 @@ def threaded_checksum(buf, chunk_bytes: int = ARG_CACHE_CHUNK, threads: Optional
 _key_memo: Dict[int, tuple] = {}  # id(tensor) -> (weakref, guard, key)
 
 
-def tensor_content_key(tensor, view) -> str:
+def tensor_content_key(tensor, view, threads: Optional[int] = None) -> str:
     """:func:`content_key` of ``view``, the contiguous bytes of ``tensor``,
     remembered per tensor object for as long as it lives and its
     ``(data_ptr, nbytes, dtype, _version)`` stay the same: hashing is the
@@ -220,7 +229,7 @@ def tensor_content_key(tensor, view) -> str:
     memo = _key_memo.get(ident)
     if memo is not None and memo[0]() is tensor and memo[1] == guard:
         return memo[2]
-    key = content_key(view)
+    key = content_key(view, threads=threads)
     ref = weakref.ref(tensor, lambda _r, ident=ident: _key_memo.pop(ident, None))
     _key_memo[ident] = (ref, guard, key)
     return key
@@ -279,7 +288,8 @@ def packed_content_key(segment_keys) -> str:
 
 
 def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
-                     buffers, buffer_meta, patch_max_fraction=None, rebase=False):
+                     buffers, buffer_meta, patch_max_fraction=None, rebase=False,
+                     retain=False):
     """The ``pack_tensor_args`` half of :func:`extract_arg_buffers`: emit the
     packed entry when the rule in its docstring holds.  Returns
     ``{id(tensor): marker}``, empty when nothing is packed.  Only called with
@@ -291,6 +301,7 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
     ``(content key, nbytes)``, ``"seg_parts"``: per segment its parts of the
     frame (the tensor's own memory and its zero padding), and the
     fraction; with ``rebase`` (``rebase_tensor_args``) also ``"rebase":
+    True``, and with ``retain`` (``retain_tensor_results``) ``"retain":
     True``."""
     import ctypes
 
@@ -370,6 +381,8 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
                 )
                 if rebase:
                     info["cache"]["rebase"] = True
+                if retain:
+                    info["cache"]["retain"] = True
     # the source tensors stay alive until the frame is drained
     buffers.append((FrameParts(parts), srcs))
     buffer_meta.append(info)
@@ -385,6 +398,7 @@ def extract_arg_buffers(
     pack_min_bytes: Optional[int] = None,
     patch_max_fraction: Optional[float] = None,
     rebase: bool = False,
+    retain: bool = False,
 ):
     """Pull large contiguous CPU torch tensors out of (args, kwargs) and
     replace them with out-of-band buffer markers (the request-direction
@@ -435,7 +449,11 @@ def extract_arg_buffers(
     ``rebase`` (the executor's ``rebase_tensor_args``, with
     ``patch_max_fraction``): such an entry is instead planned against ANY
     arena the worker holds, whatever its layout, and built there as a new
-    master that leaves the base in the cache (:meth:`_ArgCacheSend._plan_rebase`)."""
+    master that leaves the base in the cache (:meth:`_ArgCacheSend._plan_rebase`).
+
+    ``retain`` (the executor's ``retain_tensor_results``, with ``rebase``):
+    such an entry may also be rebased with an EMPTY delta, the case of a
+    subset or a reordering of what a retained result arena holds."""
     import sys
 
     if "torch" not in sys.modules:
@@ -450,7 +468,7 @@ def extract_arg_buffers(
     if to_device and pack_min_bytes is not None:
         packed_markers = _pack_small_args(
             args, kwargs, threshold, cache_min_bytes, pack_min_bytes, buffers, buffer_meta,
-            patch_max_fraction=patch_max_fraction, rebase=rebase,
+            patch_max_fraction=patch_max_fraction, rebase=rebase, retain=retain,
         )
 
     def extract(t):
@@ -505,8 +523,13 @@ def verify_result_buffers(buffer_meta, buffers) -> int:
     for i, info in enumerate(buffer_meta):
         if "sum" not in info or i >= len(buffers):
             continue
-        # looked up at call time: None when libcsp_io.so is not loaded
-        sums = native_io.checksum(buffers[i])
+        # looked up at call time: None when libcsp_io.so is not loaded.  A
+        # retained buffer may be a whole large tensor: the same two numbers,
+        # from pieces summed on the thread pool
+        if "retained" in info:
+            sums = threaded_checksum(buffers[i])
+        else:
+            sums = native_io.checksum(buffers[i])
         if sums is None:
             continue
         verified += 1
@@ -521,10 +544,12 @@ def verify_result_buffers(buffer_meta, buffers) -> int:
     return verified
 
 
-def _reconstruct(result, buffer_meta, buffers):
+def _reconstruct(result, buffer_meta, buffers, rebuilt_out=None):
     """Replace out-of-band tensor-buffer markers with rebuilt torch
     tensors (workers ship large tensors as raw frames; see
-    remote/worker_template.py protocol note).
+    remote/worker_template.py protocol note).  ``rebuilt_out`` (a dict,
+    ``retain_tensor_results``) gets the rebuilt tensors: ``i -> tensor`` for a
+    tensor buffer, ``(i, j) -> tensor`` for segment ``j`` of a packed one.
 
     A packed marker ``("__csp_packed_tensor_v1__", i, j)`` becomes tensor
     ``j`` of buffer ``i``: a zero-copy ``torch.frombuffer`` view at its
@@ -567,8 +592,10 @@ def _reconstruct(result, buffer_meta, buffers):
         # large frames arrive in a preallocated writable buffer (zero-copy
         # here); small ones as bytes (copy once into writable memory)
         data = bytearray(raw) if isinstance(raw, bytes) else raw
-        t = torch.frombuffer(data, dtype=dtype)
-        return t.reshape(info["shape"])
+        t = torch.frombuffer(data, dtype=dtype).reshape(info["shape"])
+        if rebuilt_out is not None:
+            rebuilt_out[i] = t
+        return t
 
     def walk(obj):
         if (
@@ -593,7 +620,156 @@ def _reconstruct(result, buffer_meta, buffers):
             return [walk(v) for v in obj]
         return obj
 
-    return walk(result)
+    out = walk(result)
+    if rebuilt_out is not None:
+        rebuilt_out.update(rebuilt)
+    return out
+
+
+# --- CUDA results kept in worker HBM (retain_tensor_results) ----------------
+#
+# The worker names a result buffer it keeps ("r:<op_id>:<index>", never a
+# 32-hex content key).  The dispatcher addresses cached arguments by content,
+# so that a result that went through other hands (a deep copy, covalent's own
+# serialisation) still hits: it keys the bytes it received, in the background,
+# and remembers which name holds them.
+
+
+def _forget_key(handle: WorkerHandle, key: str) -> None:
+    """``key``, a content key, is no longer believed held."""
+    handle.resident.discard(key)
+    handle.resident_arenas.pop(key, None)
+    # _ArgCacheSend is also driven with handle-like objects that carry the
+    # two resident tables alone
+    names = getattr(handle, "names", None)
+    name = names.pop(key, None) if names else None
+    if name is not None:
+        handle.retained.discard(name)
+
+
+def _forget_name(handle: WorkerHandle, name: str) -> None:
+    """``name``, a worker name, is no longer believed held (whether or not
+    its bytes have been keyed yet)."""
+    handle.retained.discard(name)
+    for key in [k for k, n in handle.names.items() if n == name]:
+        _forget_key(handle, key)
+
+
+def _tensor_view(t):
+    import ctypes
+
+    nbytes = t.numel() * t.element_size()
+    return (ctypes.c_char * nbytes).from_address(t.data_ptr()) if nbytes else b""
+
+
+def _key_retained(items):
+    """Runs on a thread: the content keys of retained buffers, computed as
+    :func:`extract_arg_buffers` will compute them for the same tensors (so the
+    per-tensor memo is seeded).  ``items``: ``(name, tensor)`` for a tensor
+    buffer, ``(name, [tensor, ...])`` for a packed one.  Returns ``[(name,
+    key, segments or None)]``.
+
+    The caller already owns these tensors.  One that torch changed in place
+    while it was hashed (its ``_version`` moved) would be registered under a
+    key of bytes that the worker's master does not hold, and only the linear
+    checksum on the reference would stand between that and a wrong hit: such a
+    buffer is left out, and is then simply never hit."""
+    out = []
+    for name, what in items:
+        tensors = what if isinstance(what, list) else [what]
+        before = [t._version for t in tensors]
+        if isinstance(what, list):
+            # one segment per pool thread, each hashed on that thread alone
+            # (a pool task that waited for pool tasks could starve the pool)
+            pairs = [(t, _tensor_view(t)) for t in what]
+            keys = _map(lambda p: tensor_content_key(p[0], p[1], threads=1), pairs, None)
+            segments = tuple((key, len(view)) for key, (_t, view) in zip(keys, pairs))
+            keyed = (name, packed_content_key(segments), segments)
+        else:
+            keyed = (name, tensor_content_key(what, _tensor_view(what)), None)
+        if [t._version for t in tensors] == before:
+            out.append(keyed)
+    return out
+
+
+async def _register_retained(handle: WorkerHandle, items, keep_segments: bool):
+    """Key ``items`` off the event loop (the chunk digests run on the hash
+    pool) and, for every name the worker is still believed to hold, make its
+    bytes addressable by content."""
+    loop = asyncio.get_running_loop()
+    try:
+        keyed = await loop.run_in_executor(None, _key_retained, items)
+    except Exception:  # noqa: BLE001 - an unkeyed result is only never hit
+        app_log.debug("keying a retained result failed", exc_info=True)
+        return
+    for name, key, segments in keyed:
+        if name not in handle.retained:
+            continue  # reported evicted, or forgotten, in the meantime
+        stale = handle.names.get(key)
+        if stale is not None and stale != name:
+            handle.retained.discard(stale)  # the same bytes, held twice
+        handle.names[key] = name
+        handle.resident.add(key)
+        if segments is not None and keep_segments:
+            handle.resident_arenas.pop(key, None)  # most recent: last
+            handle.resident_arenas[key] = segments
+
+
+def retain_results(handle: WorkerHandle, meta, rebuilt, keep_segments: bool,
+                   stats: Optional[dict] = None) -> None:
+    """After a verified reply: forget what the worker's retention pushed out
+    (``meta["retained"]["evicted"]``, so that it costs a plain store later,
+    not a miss and a resend), then note every buffer the reply marks
+    ``"retained"`` and start keying it in the background."""
+    report = meta.get("retained") or {}
+    for gone in report.get("evicted") or ():
+        if gone in handle.retained:
+            _forget_name(handle, gone)
+        else:
+            _forget_key(handle, gone)
+    items = []
+    for i, info in enumerate(meta.get("buffers") or ()):
+        name = info.get("retained")
+        if name is None:
+            continue
+        if "packed" in info:
+            tensors = [rebuilt.get((i, j)) for j in range(len(info["packed"]))]
+            if any(t is None for t in tensors):
+                continue  # a segment nobody rebuilt: cannot be keyed as B will
+            nbytes = int(info["nbytes"])
+            items.append((name, tensors))
+        else:
+            t = rebuilt.get(i)
+            if t is None:
+                continue
+            nbytes = t.numel() * t.element_size()
+            items.append((name, t))
+        _forget_name(handle, name)  # an op_id used twice: other bytes now
+        handle.retained.add(name)
+        if stats is not None:
+            stats["results_retained"] = stats.get("results_retained", 0) + 1
+            stats["results_retained_bytes"] = (
+                stats.get("results_retained_bytes", 0) + nbytes
+            )
+    if items:
+        handle.keying[:] = [task for task in handle.keying if not task.done()]
+        handle.keying.append(
+            asyncio.ensure_future(_register_retained(handle, items, keep_segments))
+        )
+
+
+async def join_retained_keying(handle: Optional[WorkerHandle] = None) -> None:
+    """Wait for the background keying of retained results: of ``handle``, or
+    of every worker of the running loop.  Afterwards their bytes are
+    addressable by content and the per-tensor key memo is seeded."""
+    loop = asyncio.get_running_loop()
+    handles = [handle] if handle is not None else list(_workers.values())
+    for h in handles:
+        pending = [t for t in h.keying if not t.done() and t.get_loop() is loop]
+        h.keying[:] = pending
+        if pending:
+            await asyncio.gather(*pending, return_exceptions=True)
+            h.keying[:] = [t for t in h.keying if not t.done()]
 
 
 def _view_nbytes(view) -> int:
@@ -621,6 +797,19 @@ class _ArgCacheSend:
         #: -1, delta FrameParts)`` when the last :meth:`frames` sent it as a
         #: rebase, else None
         self.rebases = [None] * len(entries)
+        #: worker name -> content key, for every name the last :meth:`frames`
+        #: put on the wire in place of a key (``retain_tensor_results``)
+        self.sent_as = {}
+
+    def _wire(self, key):
+        """What the worker holds ``key``'s bytes under: its own name for a
+        retained result, else the key."""
+        names = getattr(self.handle, "names", None)  # see _forget_key
+        name = names.get(key) if names else None
+        if name is None:
+            return key
+        self.sent_as[name] = key
+        return name
 
     def _plan_patch(self, cache):
         """``patch_tensor_args``: the delta that turns an arena the worker
@@ -659,7 +848,9 @@ class _ArgCacheSend:
         key, nbytes)``, wherever it lies; duplicates share one source.  The
         candidate that leaves the fewest rounded delta bytes wins, a tie goes
         to the most recent; a rebase only when they are more than none and at
-        most ``patch_max_fraction`` of the arena."""
+        most ``patch_max_fraction`` of the arena.  With ``retain_tensor_results``
+        (``cache["retain"]``) none is enough: a subset or a reordering of a
+        held arena travels as an empty delta."""
         segments = cache["segments"]
         arenas = self.handle.resident_arenas
         recent = [k for k in reversed(list(arenas)) if k in self.handle.resident]
@@ -681,7 +872,9 @@ class _ArgCacheSend:
             return None
         nbytes, base, base_nbytes, sources = best
         total = sum(-(-n // PACK_ALIGN) * PACK_ALIGN for _key, n in segments)
-        if not 0 < nbytes <= cache["patch_max_fraction"] * total:
+        if nbytes == 0 and not cache.get("retain"):
+            return None
+        if not 0 <= nbytes <= cache["patch_max_fraction"] * total:
             return None
         # cut from the tensors' own memory and the zero padding: no host copy
         delta = FrameParts(
@@ -708,8 +901,7 @@ class _ArgCacheSend:
             self.handle.resident_arenas[key] = segments
 
     def _forget(self, key):
-        self.handle.resident.discard(key)
-        self.handle.resident_arenas.pop(key, None)
+        _forget_key(self.handle, key)
 
     def frames(self, full: bool):
         """The request's frames.  A generator: the channel runs it frame by
@@ -722,6 +914,7 @@ class _ArgCacheSend:
         ]
         self.patches = [None] * len(self.entries)
         self.rebases = [None] * len(self.entries)
+        self.sent_as = {}
         wire = []
         for index, (info, key, ref) in enumerate(zip(self.entries, self.keys, self.refs)):
             if key is not None:
@@ -739,17 +932,21 @@ class _ArgCacheSend:
                 if rebase is not None:
                     info["cache"] = {
                         "key": key,
-                        "rebase": {"base": rebase[0], "base_nbytes": rebase[1],
+                        "rebase": {"base": self._wire(rebase[0]), "base_nbytes": rebase[1],
                                    "sources": rebase[2]},
                     }
                     info["rebase_nbytes"] = rebase[3].nbytes
                 elif patch is not None:
                     info["cache"] = {
-                        "key": key, "patch": {"base": patch[0], "segments": patch[1]},
+                        "key": key,
+                        "patch": {"base": self._wire(patch[0]), "segments": patch[1]},
                     }
                     info["patch_nbytes"] = patch[2].nbytes
                 else:
-                    info["cache"] = {"key": key, "ref" if ref else "store": True}
+                    info["cache"] = (
+                        {"key": self._wire(key), "ref": True} if ref
+                        else {"key": key, "store": True}
+                    )
             wire.append(info)
         yield cloudpickle.dumps(dict(self.base, arg_buffers=wire))
         for index, (view, key, ref) in enumerate(zip(self.views, self.keys, self.refs)):
@@ -772,7 +969,11 @@ class _ArgCacheSend:
         count; returns whether the worker missed a reference or the base of
         a patch."""
         report = meta.get("arg_cache") or {}
-        held = set(report.get("stored") or ()) | set(report.get("hits") or ())
+        back = self.sent_as  # the worker reports what it was sent: names
+        held = {
+            back.get(k, k)
+            for k in list(report.get("stored") or ()) + list(report.get("hits") or ())
+        }
         for key in self.keys:
             if key is not None and key not in held:
                 self._forget(key)
@@ -784,7 +985,7 @@ class _ArgCacheSend:
             if self.rebases[i] is not None:
                 # nobody can tell whether the base or the delta was wrong
                 self._forget(self.rebases[i][0])
-        done = {tuple(pair) for pair in (report.get("patched") or ())}
+        done = {(back.get(b, b), n) for b, n in (report.get("patched") or ())}
         stats = self.cache_stats
         if stats is not None:
             for view, key, patch in zip(self.views, self.keys, self.patches):
@@ -794,7 +995,7 @@ class _ArgCacheSend:
                         stats.get("arg_cache_bytes_saved", 0)
                         + _view_nbytes(view) - patch[2].nbytes
                     )
-            rebased = {tuple(pair) for pair in (report.get("rebased") or ())}
+            rebased = {(back.get(b, b), n) for b, n in (report.get("rebased") or ())}
             for view, key, rebase in zip(self.views, self.keys, self.rebases):
                 if rebase is not None and (rebase[0], key) in rebased:
                     stats["arg_cache_rebases"] = stats.get("arg_cache_rebases", 0) + 1
@@ -822,6 +1023,7 @@ async def run_task(
     arg_buffers=None,
     ack_state: Optional[dict] = None,
     cache_stats: Optional[dict] = None,
+    retain_segments: bool = False,
 ):
     """One electron through a worker.  Returns (result, exception, meta).
 
@@ -866,7 +1068,20 @@ async def run_task(
     once that frame has been written both keys are resident.  A miss on a
     rebase forgets both; the new key in ``not_stored`` forgets it alone; the
     resend never rebases.  ``cache_stats`` gets ``arg_cache_rebases``.
+
+    A verified reply whose buffers carry ``"retained"`` (the worker's
+    ``retain_tensor_results``) is noted in ``handle.retained`` and keyed in
+    the background (:func:`retain_results`); the result is handed back without
+    waiting for the hash.  Every request waits for this handle's keying before
+    it is planned, so :class:`_ArgCacheSend` sees finished names, and puts the
+    worker's name on the wire wherever it names something held: a ``ref``
+    key, the base of a patch, the base of a rebase.  ``retain_segments`` (the
+    executor's ``patch_tensor_args``): a retained arena also becomes a base
+    for patches and rebases.  ``cache_stats`` gets ``results_retained`` and
+    ``results_retained_bytes``.
     """
+    if handle.keying:
+        await join_retained_keying(handle)
     entries = arg_buffer_meta or []
     cache = None
     if entries and any("cache" in info for info in entries):
@@ -929,8 +1144,12 @@ async def run_task(
             "verified": verify_result_buffers(buffer_meta, buffers)
         }
     result, exception = cloudpickle.loads(result_blob)
+    retained = "retained" in meta
+    rebuilt = {} if retained else None
     if nbuf:
-        result = _reconstruct(result, buffer_meta, buffers)
+        result = _reconstruct(result, buffer_meta, buffers, rebuilt)
+    if retained:
+        retain_results(handle, meta, rebuilt, retain_segments, cache_stats)
     return result, exception, meta
 
 

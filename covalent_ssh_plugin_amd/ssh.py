@@ -171,6 +171,16 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # key, so alternating between states costs a delta once and hits after.
     # Replaces the in-place patch; bounded by patch_args_max_fraction.
     "rebase_tensor_args": False,
+    # With cache_tensor_args: a worker keeps the CUDA tensors it RETURNS in
+    # HBM as argument masters (one kernel launch gathers, copies and
+    # checksums them), and when a later electron on that worker takes them
+    # as arguments, whoever handled them in between, only their name
+    # travels.  Results are split into buffers where the argument side
+    # splits them: a tensor of at least min(pinned_staging_threshold_bytes,
+    # arg_cache_min_bytes) is its own buffer, smaller ones share the packed
+    # arena (pack_tensor_results).  Every retained buffer carries a checksum
+    # that the dispatcher verifies.  Shares the arg_cache_bytes budget.
+    "retain_tensor_results": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -372,6 +382,7 @@ class SSHExecutor(RemoteExecutor):
         patch_tensor_args: Optional[bool] = None,
         patch_args_max_fraction: Optional[float] = None,
         rebase_tensor_args: Optional[bool] = None,
+        retain_tensor_results: Optional[bool] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -505,6 +516,15 @@ class SSHExecutor(RemoteExecutor):
                 "packed argument arena from one that the worker holds in its "
                 "cache plus a delta"
             )
+        self.retain_tensor_results = bool(
+            _conf("retain_tensor_results", retain_tensor_results, default=False)
+        )
+        if self.retain_tensor_results and not self.cache_tensor_args:
+            raise ValueError(
+                "retain_tensor_results needs cache_tensor_args=True: a retained "
+                "result is held as a master in the worker's argument cache and "
+                "reused through its references"
+            )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -552,6 +572,10 @@ class SSHExecutor(RemoteExecutor):
             # rebase_tensor_args: packed arenas built on the worker from a
             # held arena plus a delta (the bytes left out count as saved)
             "arg_cache_rebases": 0,
+            # retain_tensor_results: result buffers the worker kept in HBM
+            # for reuse as arguments, and their bytes
+            "results_retained": 0,
+            "results_retained_bytes": 0,
         }
 
     # ------------------------------------------------------------------
@@ -987,6 +1011,9 @@ class SSHExecutor(RemoteExecutor):
             pack_results=self.pack_tensor_results,
             pack_min_bytes=self.pack_results_min_bytes,
             arg_cache_bytes=self.arg_cache_bytes if self.cache_tensor_args else 0,
+            retain_min_bytes=(
+                self.arg_cache_min_bytes if self.retain_tensor_results else None
+            ),
         )
         digest = _script_digest(text)
         key = self._pool_key()
@@ -1081,6 +1108,11 @@ class SSHExecutor(RemoteExecutor):
                         arg_buffers=arg_bufs,
                         ack_state=ack_state,
                         cache_stats=self.counters,
+                        **(
+                            {"retain_segments": self.patch_tensor_args}
+                            if self.retain_tensor_results
+                            else {}
+                        ),
                     )
                 except asyncio.TimeoutError:
                     # the worker is wedged on this task: kill it so the
@@ -1371,6 +1403,10 @@ class SSHExecutor(RemoteExecutor):
             paths: Optional[Dict[str, str]] = None
 
             if self.persistent_workers:
+                if self.retain_tensor_results:
+                    # results still being keyed in the background may be these
+                    # arguments: their keys then come from the memo, unhashed
+                    await worker_pool.join_retained_keying()
                 with timer.phase("stage"):
                     # large CPU-tensor arguments travel as raw frames, not
                     # inside the pickle (mirror of the result staging)
@@ -1394,6 +1430,7 @@ class SSHExecutor(RemoteExecutor):
                                 else None
                             ),
                             **({"rebase": True} if self.rebase_tensor_args else {}),
+                            **({"retain": True} if self.retain_tensor_results else {}),
                         )
                     )
                     function_blob = cloudpickle.dumps((function, s_args, s_kwargs))
