@@ -208,6 +208,21 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_unpack_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_unpack_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_diff_checksum_dev.restype = ctypes.c_int
+    lib.csp_diff_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_float),
+    ]
+    lib.csp_diff_block_bytes.restype = ctypes.c_size_t
+    lib.csp_diff_block_bytes.argtypes = []
+    lib.csp_diff_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_diff_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -600,6 +615,53 @@ def unpack_checksum_grid_cap(cap: int = 0) -> int:
     :func:`rebase_unpack_checksum_device` (0 restores the shipped default).
     Returns the cap in effect."""
     return int(load().csp_unpack_checksum_grid_cap(int(cap)))
+
+
+def diff_block_bytes() -> int:
+    """Bytes of one block of :func:`diff_checksum_device`."""
+    return int(load().csp_diff_block_bytes())
+
+
+def diff_checksum_device(
+    cur_ptr: int, base_ptr: int, nbytes: int, delta_ptr: int, cap_blocks: int
+) -> dict:
+    """Compare ``nbytes`` at device pointer ``cur_ptr`` with ``nbytes`` at
+    ``base_ptr`` bitwise in blocks of :func:`diff_block_bytes`, compact the
+    blocks that differ into the device buffer at ``delta_ptr`` (room for
+    ``cap_blocks * (block + 4)`` bytes) and checksum ``cur`` in the same
+    kernel launch (``delta_tensor_results``).  Returns ``{"rc", "changed",
+    "sum", "kernel_ms"}``.  ``rc`` 0: ``delta[0 : changed * (block + 4))`` is
+    the frame, the changed blocks in slot order (the last block of the
+    buffer zero padded) and then their block numbers as little-endian u32.
+    ``rc`` 1: more than ``cap_blocks`` blocks differ; ``changed`` and ``sum``
+    are valid, ``delta`` is not.  ``sum`` equals ``checksum_device(cur_ptr,
+    nbytes)``.  A null or misaligned pointer, a ``delta`` range that overlaps
+    ``cur`` or ``base`` or a block count beyond u32 raises ``GpuLibError`` and
+    launches nothing.  Runs on the library's copy stream; the two buffers
+    written on another stream must be complete first."""
+    lib = load()
+    changed = ctypes.c_uint64()
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_float()
+    rc = lib.csp_diff_checksum_dev(
+        ctypes.c_void_p(cur_ptr or None), ctypes.c_void_p(base_ptr or None), nbytes,
+        ctypes.c_void_p(delta_ptr or None), cap_blocks, ctypes.byref(changed), out,
+        ctypes.byref(kernel_ms),
+    )
+    if rc not in (0, 1):
+        _check(lib, rc, "csp_diff_checksum_dev")
+    return {
+        "rc": rc,
+        "changed": int(changed.value),
+        "sum": (int(out[0]), int(out[1])),
+        "kernel_ms": kernel_ms.value,
+    }
+
+
+def diff_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`diff_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_diff_checksum_grid_cap(int(cap)))
 
 
 def staged_d2h_bytes(data_ptr: int, nbytes: int) -> bytes:

@@ -52,15 +52,27 @@
 //                       there, or from a small delta arena, and the new arena
 //                       is written out as a new master while it is scattered
 //                       and checksummed; the held arena is only read,
+//   * csp_diff_checksum_dev
+//                     — int csp_diff_checksum_dev(const void* cur, const void*
+//                       base, size_t nbytes, void* delta, size_t cap_blocks,
+//                       uint64_t* changed, uint64_t sum[2], float* kernel_ms):
+//                       a result (cur) compared bitwise with its argument's
+//                       master (base) in blocks of csp_diff_block_bytes() =
+//                       4096; the blocks that differ are compacted into delta,
+//                       followed by their block numbers, and cur's checksum
+//                       comes from the same pass; 0 = one contiguous frame of
+//                       changed * 4100 bytes, 1 = more than cap_blocks differ
+//                       (changed and sum still valid), -1 = refused or failed,
 //   * csp_hbm_sweep_dev
 //                     — one launch of the probe's HBM sweep kernel on the
 //                       caller's buffers (tests: what the sweep copies),
 //   * csp_checksum_grid_cap / csp_copy_checksum_grid_cap /
-//     csp_unpack_checksum_grid_cap / csp_pack_checksum_grid_cap
+//     csp_unpack_checksum_grid_cap / csp_pack_checksum_grid_cap /
+//     csp_diff_checksum_grid_cap
 //                     — tools only: the grid caps of the checksum, copy,
-//                       unpack and pack-with-checksum kernels (the patch and
-//                       rebase kernels share the unpack kernel's), so tests
-//                       reach every loop on tiny data.
+//                       unpack, pack-with-checksum and diff kernels (the patch
+//                       and rebase kernels share the unpack kernel's), so
+//                       tests reach every loop on tiny data.
 //
 // Kernel design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
 //   - wave64; 256-thread blocks = 4 waves;
@@ -2695,6 +2707,292 @@ extern "C" int csp_rebase_unpack_checksum_dev(const void* base, size_t base_byte
 #undef REBASE_TRY
     out[0] = host[0];
     out[1] = host[1];
+    return done(0);
+}
+
+// ---------------------------------------------------------------------------
+// Result delta: a result diffed against its argument master, blocks compacted
+// ---------------------------------------------------------------------------
+//
+// An iterative electron returns state it took as an argument with little of
+// it changed.  The argument's master is still in HBM, the result is in HBM,
+// and the dispatcher still holds the argument's bytes: only the blocks that
+// differ have to cross the pipe.  This kernel reads `cur` (the result) and
+// `base` (the master) exactly once, writes neither, and in the same pass
+//
+//   - compares them block by block, bitwise (an XOR fold and a wave vote:
+//     +0.0 differs from -0.0, equal NaN payloads are equal),
+//   - compacts the blocks that differ into `delta`, and
+//   - computes csp_checksum_dev(cur, nbytes), which is what lets the
+//     dispatcher prove its reconstruction.
+//
+// Work split: a block is kDiffBlockBytes = 4096 bytes = one wave64 x 16 bytes
+// per lane x the unroll of 4 (a design constant, not a measurement).  A wave
+// owns whole blocks and walks them wave-stride over the grid (256-thread
+// workgroups, four waves, at most 1024 workgroups like the other
+// checksum-carrying kernels).  Per block a lane issues its 4 loads of `cur`
+// and its 4 of `base` together, 8 in flight; `base` loads are plain (later
+// hits read the master again), and so are `cur` loads: with retention `cur`
+// is itself a master, and measured against nontemporal loads plain is level
+// up to 64 MiB and 6 to 8 % behind only on a 1 GiB result, 0.03 ms of a round
+// trip of hundreds (profiles/delta_results.md).
+//
+// Compaction: in a wave whose block differs lane 0 takes a slot with one
+// atomicAdd on a device counter and a shuffle hands it to the wave.  A slot
+// below cap_blocks gets the wave's four vectors, still in registers, as
+// nontemporal 16-byte stores at delta + slot * 4096, and the block number as
+// a u32 at index[slot]; a slot at or beyond the cap writes nothing while the
+// counter keeps counting.  Slot order is whatever the atomics gave: the price
+// of one pass, and the index says what each slot is.
+//
+// Edges: vectors past nbytes / 16 are neither loaded nor compared and are
+// stored as zero; the nbytes % 16 tail bytes are read one by one by the lane
+// that owns that vector, into a zero-padded vector that is compared, summed
+// (a zero adds nothing, so the sum is csp_checksum_kernel's) and stored like
+// any other.  No byte at or after cur + nbytes or base + nbytes is read.
+static const size_t kDiffBlockBytes = 4096;
+static const size_t kDiffBlockVecs = kDiffBlockBytes / 16;  // 256
+static_assert(kDiffBlockBytes == 64 * 16 * kChecksumUnroll, "one wave, 16 B per lane, unroll 4");
+
+// the zero-padded vector of the `tail` (1..15) bytes at p
+__device__ __forceinline__ u32x4 diff_load_tail(const unsigned char* p, unsigned int tail) {
+    unsigned int w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (unsigned int b = 0; b < 15; ++b)
+        if (b < tail) w[b >> 2] |= (unsigned int)p[b] << (8 * (b & 3));
+    u32x4 v;
+    v[0] = w[0]; v[1] = w[1]; v[2] = w[2]; v[3] = w[3];
+    return v;
+}
+
+__global__ __launch_bounds__(256) void csp_diff_checksum_kernel(
+    const u32x4* __restrict__ cur, const u32x4* __restrict__ base, size_t n16,
+    unsigned int tail_bytes, size_t nblocks, u32x4* __restrict__ delta, size_t cap_blocks,
+    unsigned int* __restrict__ index, unsigned long long* __restrict__ out) {
+    const unsigned int lane = threadIdx.x & 63;
+    const size_t nwaves = (size_t)gridDim.x * 4;
+    unsigned long long s0 = 0, t = 0;
+    // blk depends on the wave alone: votes and shuffles see all 64 lanes
+    for (size_t blk = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); blk < nblocks; blk += nwaves) {
+        const size_t v0 = blk * kDiffBlockVecs + lane;
+        u32x4 c[kChecksumUnroll], b[kChecksumUnroll];
+        if ((blk + 1) * kDiffBlockVecs <= n16) {
+#pragma unroll
+            for (int u = 0; u < kChecksumUnroll; ++u) c[u] = cur[v0 + u * 64];
+#pragma unroll
+            for (int u = 0; u < kChecksumUnroll; ++u) b[u] = base[v0 + u * 64];
+        } else {  // the last, short block
+#pragma unroll
+            for (int u = 0; u < kChecksumUnroll; ++u) {
+                const size_t vi = v0 + u * 64;
+                c[u] = b[u] = u32x4{0, 0, 0, 0};
+                if (vi < n16) {
+                    c[u] = cur[vi];
+                    b[u] = base[vi];
+                } else if (vi == n16 && tail_bytes != 0) {
+                    c[u] = diff_load_tail(reinterpret_cast<const unsigned char*>(cur + n16),
+                                          tail_bytes);
+                    b[u] = diff_load_tail(reinterpret_cast<const unsigned char*>(base + n16),
+                                          tail_bytes);
+                }
+            }
+        }
+        unsigned int x = 0;
+#pragma unroll
+        for (int u = 0; u < kChecksumUnroll; ++u) {
+            const u32x4 d = c[u] ^ b[u];
+            x |= d[0] | d[1] | d[2] | d[3];
+            checksum_add(s0, t, c[u], (unsigned int)((v0 + u * 64) * 4));
+        }
+        if (__ballot(x != 0) != 0) {
+            unsigned long long slot = 0;
+            if (lane == 0) slot = atomicAdd(&out[2], 1ull);
+            slot = __shfl(slot, 0, 64);
+            if (slot < cap_blocks) {
+                u32x4* d = delta + slot * kDiffBlockVecs + lane;
+#pragma unroll
+                for (int u = 0; u < kChecksumUnroll; ++u)
+                    __builtin_nontemporal_store(c[u], &d[u * 64]);
+                if (lane == 0) index[slot] = (unsigned int)blk;
+            }
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+static const size_t kDiffGridCapDefault = 1024;
+static size_t g_diff_grid_cap = kDiffGridCapDefault;
+
+// Tools only: the grid cap of the next csp_diff_checksum_dev calls (0 restores
+// the default).  Returns the cap in effect.  With a cap of 1, 2 or 3
+// workgroups a few dozen blocks make every wave take several trips.
+extern "C" size_t csp_diff_checksum_grid_cap(size_t cap) {
+    g_diff_grid_cap = cap ? std::min(cap, size_t(65536)) : kDiffGridCapDefault;
+    return g_diff_grid_cap;
+}
+
+extern "C" size_t csp_diff_block_bytes() { return kDiffBlockBytes; }
+
+// Diff nbytes at device pointer cur against nbytes at device pointer base in
+// blocks of csp_diff_block_bytes(), put csp_checksum_dev(cur, nbytes) into
+// sum[2] and the number of blocks that differ into *changed.
+//
+//   0: changed <= cap_blocks, and delta[0 : changed * 4100) is one contiguous
+//      frame: the changed blocks (the last one zero padded) in slot order,
+//      then their block numbers as little-endian u32 in the same order,
+//   1: more blocks differ than cap_blocks; *changed and sum are valid, the
+//      contents of delta are unspecified.  Not an error,
+//  -1: with a message and nothing launched, for a null pointer, a cur, base
+//      or delta that is not 16-byte aligned, a delta range [delta, delta +
+//      cap_blocks * 4100) that overlaps cur or base, or a block count that
+//      does not fit in a u32; and for a HIP failure.
+//
+// nbytes == 0 returns 0 with zero sums and changed = 0.  No byte outside
+// delta's range is written.  The counter sits beside the accumulators and the
+// index scratch is library-owned, grown on demand.  Runs on copy_stream() and
+// synchronises it before returning; cur and base written on another stream
+// must be complete first.  kernel_ms (optional): the kernel alone, from events
+// around the launch.
+extern "C" int csp_diff_checksum_dev(const void* cur, const void* base, size_t nbytes,
+                                     void* delta, size_t cap_blocks, uint64_t* changed,
+                                     uint64_t sum[2], float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (changed == nullptr || sum == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_diff_checksum_dev: null output pointer");
+        return -1;
+    }
+    *changed = 0;
+    sum[0] = sum[1] = 0;
+    if (nbytes == 0) return 0;
+    const uintptr_t c = reinterpret_cast<uintptr_t>(cur);
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+    const uintptr_t d = reinterpret_cast<uintptr_t>(delta);
+    if (c == 0 || b == 0 || d == 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_diff_checksum_dev: null pointer among cur %p, base %p and delta %p", cur,
+                 base, delta);
+        return -1;
+    }
+    if (c % 16 != 0 || b % 16 != 0 || d % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_diff_checksum_dev: cur %p, base %p and delta %p must be 16-byte aligned",
+                 cur, base, delta);
+        return -1;
+    }
+    const size_t nblocks = nbytes / kDiffBlockBytes + (nbytes % kDiffBlockBytes != 0);
+    if (nblocks > size_t(0xFFFFFFFFu)) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_diff_checksum_dev: %zu blocks of %zu bytes do not fit in a u32", nblocks,
+                 nbytes);
+        return -1;
+    }
+    // a cap above the block count can never be reached: the kernel and the
+    // index scratch need no more.  The overlap test takes the whole range the
+    // caller handed over, cap_blocks * 4100 bytes; an empty one overlaps nothing
+    const size_t cap = std::min(cap_blocks, nblocks);
+    const size_t delta_bytes = cap_blocks * (kDiffBlockBytes + 4);
+    if (cap_blocks > (~size_t(0)) / (kDiffBlockBytes + 4) || c + nbytes < c || b + nbytes < b ||
+        d + delta_bytes < d) {
+        snprintf(g_err, sizeof(g_err), "csp_diff_checksum_dev: a range overflows");
+        return -1;
+    }
+    if (delta_bytes != 0 &&
+        ((d < c + nbytes && c < d + delta_bytes) || (d < b + nbytes && b < d + delta_bytes))) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_diff_checksum_dev: %zu bytes at delta %p overlap %zu bytes at cur %p or "
+                 "base %p", delta_bytes, delta, nbytes, cur, base);
+        return -1;
+    }
+
+    // two sums and the slot counter, and one grow-only index scratch per
+    // process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static unsigned int* index = nullptr;
+    static size_t index_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_device != device) {
+        if (acc) (void)hipFree(acc);
+        if (index) (void)hipFree(index);
+        acc = nullptr;
+        index = nullptr;
+        index_cap = 0;
+        dev_device = device;
+    }
+    if (acc == nullptr) HIP_TRY(hipMalloc(&acc, 3 * sizeof(unsigned long long)));
+    if (index == nullptr || index_cap < cap) {
+        if (index) (void)hipFree(index);
+        index = nullptr;
+        index_cap = 0;
+        size_t grown = 1024;
+        while (grown < cap) grown *= 2;
+        HIP_TRY(hipMalloc(&index, grown * sizeof(unsigned int)));
+        index_cap = grown;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define DIFF_TRY(expr)                                             \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    DIFF_TRY(hipMemsetAsync(acc, 0, 3 * sizeof(unsigned long long), s));
+    const size_t n16 = nbytes / 16;
+    const unsigned int tail_bytes = (unsigned int)(nbytes % 16);
+    const size_t blocks = std::min((nblocks + 3) / 4, g_diff_grid_cap);
+    if (t0) DIFF_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_diff_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       static_cast<const u32x4*>(cur), static_cast<const u32x4*>(base), n16,
+                       tail_bytes, nblocks, static_cast<u32x4*>(delta), cap, index, acc);
+    DIFF_TRY(hipGetLastError());
+    if (t1) DIFF_TRY(hipEventRecord(t1, s));
+    unsigned long long host[3] = {0, 0, 0};
+    DIFF_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    DIFF_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) DIFF_TRY(hipEventElapsedTime(kernel_ms, t0, t1));
+    sum[0] = host[0];
+    sum[1] = host[1];
+    *changed = host[2];
+    if (host[2] > cap_blocks) return done(1);
+    if (host[2] > 0) {
+        // the index follows the blocks: one contiguous frame
+        DIFF_TRY(hipMemcpyAsync(static_cast<unsigned char*>(delta) + host[2] * kDiffBlockBytes,
+                                index, host[2] * sizeof(unsigned int),
+                                hipMemcpyDeviceToDevice, s));
+        DIFF_TRY(hipStreamSynchronize(s));
+    }
+#undef DIFF_TRY
     return done(0);
 }
 

@@ -72,6 +72,7 @@ def render_worker(
     pack_min_bytes: int = 0,
     arg_cache_bytes: int = 0,
     retain_min_bytes: Optional[int] = None,
+    delta_max_fraction: Optional[float] = None,
 ) -> str:
     """Return the persistent worker script text (one per endpoint; the
     GPU slot arrives via the CSP_GPU_SLOT env var at launch).  With
@@ -84,7 +85,11 @@ def render_worker(
     (``cache_tensor_args``); 0 means no cache.  ``retain_min_bytes``
     (``retain_tensor_results``; ``None`` is off) is the executor's
     ``arg_cache_min_bytes``: the worker keeps CUDA result buffers as argument
-    masters in that cache, split where the argument side splits them."""
+    masters in that cache, split where the argument side splits them.
+    ``delta_max_fraction`` (``delta_tensor_results``; ``None`` is off) is the
+    executor's ``patch_args_max_fraction``: a CUDA result buffer of which at
+    most that share of the blocks differs from the cached argument of the
+    same size leaves as a block delta."""
     text = _template_text(str(_WORKER_TEMPLATE_PATH))
     thr = DEFAULT_STAGING_THRESHOLD if staging_threshold is None else int(staging_threshold)
     replacements = {
@@ -100,6 +105,9 @@ def render_worker(
         "__CSP_PACK_MIN_BYTES__": str(int(pack_min_bytes)),
         "__CSP_ARG_CACHE_BYTES__": str(int(arg_cache_bytes)),
         "__CSP_RETAIN_MIN_BYTES__": str(-1 if retain_min_bytes is None else int(retain_min_bytes)),
+        "__CSP_DELTA_MAX_FRACTION__": repr(
+            -1.0 if delta_max_fraction is None else float(delta_max_fraction)
+        ),
     }
     for token, value in replacements.items():
         text = text.replace(token, value)

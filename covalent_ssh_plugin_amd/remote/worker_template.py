@@ -142,6 +142,12 @@ ARG_CACHE_BYTES = int(__CSP_ARG_CACHE_BYTES__)
 # retain_tensor_results): the executor's arg_cache_min_bytes, so that results
 # are split into buffers where the argument side splits them; -1 = off.
 RETAIN_MIN_BYTES = int(__CSP_RETAIN_MIN_BYTES__)
+# Send a CUDA result buffer as a block delta against the cached argument of
+# the same size (executor option delta_tensor_results) when at most this
+# fraction of its blocks changed: the executor's patch_args_max_fraction;
+# negative = off.
+DELTA_MAX_FRACTION = float(__CSP_DELTA_MAX_FRACTION__)
+DELTA_BLOCK = 4096  # csp_diff_block_bytes()
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
 # break the children) and every electron executes in a freshly forked
@@ -306,6 +312,18 @@ def _load_gpu_lib():
             ctypes.c_size_t,
             ctypes.POINTER(ctypes.c_uint64),
             ctypes.POINTER(ctypes.c_double),
+        ]
+    if DELTA_MAX_FRACTION >= 0:
+        lib.csp_diff_checksum_dev.restype = ctypes.c_int
+        lib.csp_diff_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_float),
         ]
     lib.csp_patch_unpack_checksum_dev.restype = ctypes.c_int
     lib.csp_patch_unpack_checksum_dev.argtypes = [
@@ -753,6 +771,76 @@ def _stage_result(result, stats, buffers, buffer_meta, retain=None):
     return staged
 
 
+def _delta_results(lib, masters, buffers, buffer_meta, stats):
+    """After staging (delta_tensor_results): a CUDA result buffer that has the
+    byte count of one of the request's argument masters is compared with it on
+    the GPU, and when few enough of its blocks differ only those travel.
+
+    ``masters``: (argument entry index, master, nbytes) per cached argument
+    entry, in argument order.  A ``_DeferredCuda`` buffer of at least
+    RETAIN_MIN_BYTES (retention on) or STAGING_THRESHOLD bytes is paired with
+    the first master of exactly its byte count that no earlier buffer took.
+    ONE csp_diff_checksum_dev call with room for floor(DELTA_MAX_FRACTION *
+    blocks) blocks then yields the frame and the checksum of the whole buffer.
+    Within the cap the entry is replaced by the frame and its meta names the
+    argument; beyond it the buffer goes whole, now with a checksum.  A
+    refusal, an error or a failed allocation leaves the buffer as it was, the
+    reason in stats["delta_fallback"]: a delta never fails a task."""
+    import ctypes
+
+    import torch
+
+    floor = max(1, RETAIN_MIN_BYTES if RETAIN_MIN_BYTES >= 0 else STAGING_THRESHOLD)
+    used = set()
+    t0 = time.monotonic()
+    stats.update(delta_buffers=0, delta_bytes=0, delta_full_bytes=0)
+    for i, (view, _keep) in enumerate(buffers):
+        if not isinstance(view, _DeferredCuda) or view.nbytes < floor:
+            continue
+        pair = next(
+            (k for k, m in enumerate(masters) if k not in used and m[2] == view.nbytes),
+            None,
+        )
+        if pair is None:
+            continue
+        used.add(pair)
+        arg_index, master, nbytes = masters[pair]
+        cap = int(DELTA_MAX_FRACTION * ((nbytes + DELTA_BLOCK - 1) // DELTA_BLOCK))
+        try:
+            delta = torch.empty(
+                max(16, cap * (DELTA_BLOCK + 4)), dtype=torch.uint8, device="cuda"
+            )
+            changed = ctypes.c_uint64()
+            sums = (ctypes.c_uint64 * 2)()
+            rc = lib.csp_diff_checksum_dev(
+                ctypes.c_void_p(view.ptr), ctypes.c_void_p(master.data_ptr()), nbytes,
+                ctypes.c_void_p(delta.data_ptr()), cap, ctypes.byref(changed), sums, None,
+            )
+            if rc not in (0, 1):
+                raise RuntimeError(
+                    "csp_diff_checksum_dev failed (rc=%d): %s"
+                    % (rc, lib.csp_last_error().decode(errors="replace"))
+                )
+        except Exception as e:  # noqa: BLE001 - a delta never fails a task
+            stats["delta_fallback"] = repr(e)[:500]
+            continue
+        buffer_meta[i].setdefault("sum", [int(sums[0]), int(sums[1])])
+        if rc == 1:
+            continue  # too much changed: whole, as without the option
+        count = int(changed.value)
+        wire = count * (DELTA_BLOCK + 4)
+        # the frame keeps the delta buffer alive; a retained master stays in
+        # the cache, anything else is let go with the old entry
+        buffers[i] = (_DeferredCuda(lib, delta.data_ptr(), wire), delta)
+        buffer_meta[i]["delta"] = {
+            "arg": arg_index, "block": DELTA_BLOCK, "changed": count, "nbytes": nbytes,
+        }
+        stats["delta_buffers"] += 1
+        stats["delta_bytes"] += wire
+        stats["delta_full_bytes"] += nbytes
+    stats["delta_ms"] = round((time.monotonic() - t0) * 1000, 3)
+
+
 def _read_frame(fd, idle_timeout=0.0):
     if idle_timeout > 0:
         import select
@@ -865,6 +953,10 @@ def _compare_arg_sum(index, got, info, nbytes):
 
 _arg_cache = collections.OrderedDict()
 _arg_cache_resident = 0  # bytes held by the masters
+# (argument entry index, master, nbytes) for every entry of the request in
+# hand that ended up as a master (store, hit, patch or rebase), in argument
+# order: what a result buffer can be diffed against (_delta_results)
+_request_masters = []
 
 
 def _new_arg_cache_report():
@@ -1613,6 +1705,7 @@ def _receive_arg_frames(arg_meta):
     stage = _new_arg_stage()
     error = None
     report = None
+    del _request_masters[:]
     if any(info.get("cache") for info in arg_meta):
         report = _new_arg_cache_report()
     for index, info in enumerate(arg_meta):
@@ -1624,6 +1717,9 @@ def _receive_arg_frames(arg_meta):
                 frames.append(
                     receive(index, info, stage, report or _new_arg_cache_report())
                 )
+                held = _arg_cache.get((info.get("cache") or {}).get("key"))
+                if DELTA_MAX_FRACTION >= 0 and held is not None:
+                    _request_masters.append((index, held[0], held[1]))
             except Exception as e:  # noqa: BLE001
                 frames.append(None)
                 if error is None:
@@ -1815,6 +1911,9 @@ def _serve_one(request):
             meta["retained"] = retain["report"]
         try:
             result = _stage_result(result, stats, buffers, meta["buffers"], retain)
+            if (DELTA_MAX_FRACTION >= 0 and ARG_CACHE_BYTES > 0 and not ISOLATE
+                    and _request_masters and _gpu_lib is not None):
+                _delta_results(_gpu_lib, _request_masters, buffers, meta["buffers"], stats)
             meta["staging"] = stats
         except Exception as e:  # noqa: BLE001
             result, exception, buffers = None, e, []
@@ -1976,6 +2075,7 @@ def main():
             _send_buffer(_proto_fd, view)
         del buffers
         request = None  # lets go of device arguments before the next wait
+        del _request_masters[:]
         if _gpu_lib is not None:
             _gpu_lib.csp_staging_release_all()
 

@@ -525,8 +525,9 @@ def verify_result_buffers(buffer_meta, buffers) -> int:
             continue
         # looked up at call time: None when libcsp_io.so is not loaded.  A
         # retained buffer may be a whole large tensor: the same two numbers,
-        # from pieces summed on the thread pool
-        if "retained" in info:
+        # from pieces summed on the thread pool; so may one rebuilt from a
+        # delta (delta_tensor_results)
+        if "retained" in info or "delta" in info:
             sums = threaded_checksum(buffers[i])
         else:
             sums = native_io.checksum(buffers[i])
@@ -536,12 +537,70 @@ def verify_result_buffers(buffer_meta, buffers) -> int:
         got = [int(sums[0]), int(sums[1])]
         want = [int(info["sum"][0]), int(info["sum"][1])]
         if got != want:
+            how = ""
+            if "delta" in info:
+                how = f", rebuilt from a delta against argument {info['delta'].get('arg')},"
             raise RuntimeError(
-                f"result buffer {i} failed its integrity check: the worker "
+                f"result buffer {i}{how} failed its integrity check: the worker "
                 f"sent checksum {want}, the {memoryview(buffers[i]).nbytes} "
                 f"bytes received give {got}"
             )
     return verified
+
+
+def apply_result_delta(info, frame, base_view) -> bytearray:
+    """Rebuild a result buffer that the worker sent as a block delta against
+    one of the request's arguments (``delta_tensor_results``).
+
+    ``info`` is the buffer's ``"delta"`` meta: ``{"arg", "block", "changed",
+    "nbytes"}``.  ``frame`` holds the ``changed`` blocks of ``block`` bytes in
+    the worker's slot order (the buffer's last block zero padded), then their
+    block numbers as little-endian u32 in the same order.  ``base_view`` is
+    the argument as it was sent: a buffer, or the :class:`FrameParts` of a
+    packed arena, taken in order and zero padded to ``nbytes``.  Returns
+    ``nbytes`` of writable memory: the base with the blocks laid over it, the
+    last one cut to length.
+
+    A frame of another length, a block number beyond the buffer or one that
+    appears twice raises the ``RuntimeError`` of a failed integrity check.
+    That the result is the worker's is proved afterwards by the worker's
+    checksum of the whole buffer (:func:`verify_result_buffers`), and with it
+    the base, the index and every block."""
+    import numpy as np
+
+    block, changed, nbytes = int(info["block"]), int(info["changed"]), int(info["nbytes"])
+    frame = memoryview(frame).cast("B")
+    nblocks = -(-nbytes // block) if block > 0 else 0
+    problem = None
+    if block <= 0 or changed < 0 or changed * (block + 4) != frame.nbytes:
+        problem = (
+            f"{changed} blocks of {block} bytes and their index need "
+            f"{changed * (block + 4)} bytes, the frame has {frame.nbytes}"
+        )
+    else:
+        index = np.frombuffer(frame[changed * block :], dtype="<u4")
+        if changed and int(index.max()) >= nblocks:
+            problem = f"block {int(index.max())} is beyond the buffer's {nblocks} blocks"
+        elif len(np.unique(index)) != changed:
+            problem = "a block number appears twice"
+    if problem is not None:
+        raise RuntimeError(
+            f"result buffer sent as a delta against argument {info.get('arg')} "
+            f"failed its integrity check: {problem}"
+        )
+    out = bytearray()
+    for part in base_view.parts if isinstance(base_view, FrameParts) else [base_view]:
+        out += memoryview(part).cast("B")
+    del out[nbytes:]
+    out.extend(bytes(nblocks * block - len(out)))  # whole blocks; cut to nbytes below
+    if changed:
+        blocks = np.frombuffer(out, dtype=np.uint8).reshape(nblocks, block)
+        blocks[index] = np.frombuffer(frame[: changed * block], dtype=np.uint8).reshape(
+            changed, block
+        )
+        del blocks  # the bytearray cannot shrink while numpy exports it
+    del out[nbytes:]
+    return out
 
 
 def _reconstruct(result, buffer_meta, buffers, rebuilt_out=None):
@@ -1139,6 +1198,24 @@ async def run_task(
         if ack_state is not None:
             ack_state["started"] = False
     buffer_meta = meta.get("buffers", [])
+    for i, info in enumerate(buffer_meta[: len(buffers)] if nbuf else []):
+        # delta_tensor_results: the bytes of the argument it was diffed
+        # against are still in hand; the checksum below proves the result
+        if "delta" in info:
+            views = cache.views if cache is not None else []
+            arg = int(info["delta"]["arg"])
+            if not 0 <= arg < len(views):
+                raise RuntimeError(
+                    f"result buffer {i} sent as a delta failed its integrity check: "
+                    f"the request has no argument {arg}"
+                )
+            wire = memoryview(buffers[i]).nbytes
+            buffers[i] = apply_result_delta(info["delta"], buffers[i], views[arg])
+            if cache_stats is not None:
+                cache_stats["result_deltas"] = cache_stats.get("result_deltas", 0) + 1
+                cache_stats["result_delta_bytes_saved"] = (
+                    cache_stats.get("result_delta_bytes_saved", 0) + len(buffers[i]) - wire
+                )
     if nbuf and any("sum" in info for info in buffer_meta):
         meta["result_integrity"] = {
             "verified": verify_result_buffers(buffer_meta, buffers)

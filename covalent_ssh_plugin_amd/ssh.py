@@ -181,6 +181,14 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # arena (pack_tensor_results).  Every retained buffer carries a checksum
     # that the dispatcher verifies.  Shares the arg_cache_bytes budget.
     "retain_tensor_results": False,
+    # With cache_tensor_args: a CUDA result buffer that has the byte count of
+    # one of the electron's cached arguments is compared with that argument's
+    # master on the GPU in 4 KiB blocks, in the kernel launch that checksums
+    # it, and when at most patch_args_max_fraction of the blocks differ only
+    # those travel; the dispatcher lays them over the argument bytes it still
+    # holds and verifies the whole buffer.  For iterative electrons that hand
+    # back most of their state unchanged.
+    "delta_tensor_results": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -383,6 +391,7 @@ class SSHExecutor(RemoteExecutor):
         patch_args_max_fraction: Optional[float] = None,
         rebase_tensor_args: Optional[bool] = None,
         retain_tensor_results: Optional[bool] = None,
+        delta_tensor_results: Optional[bool] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -525,6 +534,15 @@ class SSHExecutor(RemoteExecutor):
                 "result is held as a master in the worker's argument cache and "
                 "reused through its references"
             )
+        self.delta_tensor_results = bool(
+            _conf("delta_tensor_results", delta_tensor_results, default=False)
+        )
+        if self.delta_tensor_results and not self.cache_tensor_args:
+            raise ValueError(
+                "delta_tensor_results needs cache_tensor_args=True: a result is "
+                "sent as a delta against an argument master in the worker's "
+                "argument cache"
+            )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -576,6 +594,10 @@ class SSHExecutor(RemoteExecutor):
             # for reuse as arguments, and their bytes
             "results_retained": 0,
             "results_retained_bytes": 0,
+            # delta_tensor_results: result buffers that arrived as a block
+            # delta against an argument, and the bytes the delta left out
+            "result_deltas": 0,
+            "result_delta_bytes_saved": 0,
         }
 
     # ------------------------------------------------------------------
@@ -1013,6 +1035,9 @@ class SSHExecutor(RemoteExecutor):
             arg_cache_bytes=self.arg_cache_bytes if self.cache_tensor_args else 0,
             retain_min_bytes=(
                 self.arg_cache_min_bytes if self.retain_tensor_results else None
+            ),
+            delta_max_fraction=(
+                self.patch_args_max_fraction if self.delta_tensor_results else None
             ),
         )
         digest = _script_digest(text)
