@@ -25,6 +25,9 @@ gfx950 only) provides:
   layout, each segment from a held arena or from a small delta arena, written
   out as a new master while the held one is only read
   (``rebase_tensor_args``),
+* ``csp_gather_checksum_dev`` — one strided device tensor written in
+  row-major order to a contiguous buffer, with that buffer's checksum from the
+  same launch (``gather_tensor_results``),
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
   ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
@@ -223,6 +226,23 @@ def load(path: str = "") -> ctypes.CDLL:
     lib.csp_diff_block_bytes.argtypes = []
     lib.csp_diff_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_diff_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_gather_checksum_dev.restype = ctypes.c_int
+    lib.csp_gather_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_uint,
+        ctypes.c_uint,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_int),
+    ]
+    lib.csp_gather_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_gather_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_gather_checksum_path.restype = ctypes.c_int
+    lib.csp_gather_checksum_path.argtypes = [ctypes.c_int]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -662,6 +682,61 @@ def diff_checksum_grid_cap(cap: int = 0) -> int:
     """Tools only: set the grid cap of :func:`diff_checksum_device` (0
     restores the shipped default).  Returns the cap in effect."""
     return int(load().csp_diff_checksum_grid_cap(int(cap)))
+
+
+GATHER_PATHS = {0: "none", 1: "direct", 2: "direct16", 3: "transpose"}
+
+
+def gather_checksum_device(
+    src_ptr: int, elem_size: int, sizes, strides, dst_ptr: int, dst_bytes: int
+) -> dict:
+    """Write the strided device tensor at ``src_ptr`` (``sizes`` and
+    ``strides`` in elements of ``elem_size`` bytes, as torch gives them) in
+    row-major order to the 16-byte aligned device buffer at ``dst_ptr`` and
+    checksum that buffer in the same kernel launch
+    (``gather_tensor_results``).  ``dst_bytes`` is the data rounded up to 16;
+    the padding is stored as zero.  Returns ``{"sums": (s0, s1), "kernel_ms",
+    "path"}``: ``sums`` equals ``checksum_device(dst_ptr, dst_bytes)``,
+    ``path`` is ``"direct"`` (per-element loads), ``"direct16"`` (16-byte
+    loads), ``"transpose"`` (through an LDS tile) or ``"none"`` (no element).
+    An element size outside 1, 2, 4, 8, 16, more than 4 dimensions after
+    collapsing, a null or misaligned pointer, a wrong ``dst_bytes`` or a source
+    extent that overlaps the destination raises ``GpuLibError`` and launches
+    nothing.  Runs on the library's copy stream; a source written on another
+    stream must be complete (``torch.cuda.synchronize()``) first."""
+    lib = load()
+    n = len(sizes)
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    path = ctypes.c_int()
+    _check(
+        lib,
+        lib.csp_gather_checksum_dev(
+            ctypes.c_void_p(src_ptr or None), elem_size, n,
+            (ctypes.c_uint64 * n)(*[int(v) for v in sizes]),
+            (ctypes.c_uint64 * n)(*[int(v) for v in strides]),
+            ctypes.c_void_p(dst_ptr or None), dst_bytes, out,
+            ctypes.byref(kernel_ms), ctypes.byref(path),
+        ),
+        "csp_gather_checksum_dev",
+    )
+    return {
+        "sums": (int(out[0]), int(out[1])),
+        "kernel_ms": kernel_ms.value,
+        "path": GATHER_PATHS[path.value],
+    }
+
+
+def gather_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`gather_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_gather_checksum_grid_cap(int(cap)))
+
+
+def gather_checksum_path(force: int = 0) -> int:
+    """Tools only: 1 forces the direct path of :func:`gather_checksum_device`,
+    0 restores the host's choice.  Returns the value in effect."""
+    return int(load().csp_gather_checksum_path(int(force)))
 
 
 def staged_d2h_bytes(data_ptr: int, nbytes: int) -> bytes:

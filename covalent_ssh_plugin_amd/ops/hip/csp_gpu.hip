@@ -2996,6 +2996,566 @@ extern "C" int csp_diff_checksum_dev(const void* cur, const void* base, size_t n
     return done(0);
 }
 
+// ---------------------------------------------------------------------------
+// Strided gather with checksum: a non-contiguous result laid out in one pass
+// ---------------------------------------------------------------------------
+//
+// A CUDA result that is a transpose, a permute, a column slice, channels_last
+// or a strided subsample is written in row-major order into a contiguous
+// destination (a retained master, or the buffer its frame is streamed from)
+// by ONE launch that also yields csp_checksum_dev(dst, dst_bytes): one HBM
+// read and one write, where contiguous() followed by csp_pack_checksum_dev
+// reads twice, writes twice and allocates twice.
+//
+// The host drops size-1 dimensions and merges neighbours that are contiguous
+// with each other, refuses what is left above 4 dimensions, and picks one of
+// two paths per call, so the choice is uniform for every wave:
+//
+//   - DIRECT: the pack kernel's decomposition of the OUTPUT: 16 KiB tiles,
+//     256 threads, four 16-byte vectors per lane, blocks looping
+//     tile += gridDim.x.  A lane owns whole output vectors: it splits the
+//     vector's first element index into coordinates once (32-bit divisions
+//     when numel < 2^32), then walks element by element with carries across
+//     row ends, assembles the vector in registers, stores it once with an
+//     aligned 16-byte store and sums it with checksum_add at its output word
+//     index.  Elements past numel in the last vector are zeros: the padding.
+//     Loads are per element at the element size.  Correct for every valid
+//     input, an inner stride other than 1 and stride 0 included.
+//     16-byte sub-path: when the inner stride is 1, the inner run is a
+//     multiple of 16 bytes and the base and all outer strides keep 16-byte
+//     alignment, the host re-expresses the tensor in 16-byte elements, and
+//     the same kernel then issues one 16-byte load per vector;
+//   - TRANSPOSE: taken when the innermost output dimension C has a source
+//     stride other than 1, another dimension U has source stride 1, and both
+//     hold at least kGatherTransposeMin elements.  A workgroup owns a
+//     TU x TC patch of the (U, C) plane for fixed remaining coordinates and
+//     loops patch += gridDim.x.  It loads the patch with lanes running along
+//     U (coalesced in the source) into an LDS tile tile[c][u]; after a barrier
+//     lanes run along C: a lane owns 16-byte windows of one output row, reads
+//     their elements down an LDS column and stores the window.  The row pitch
+//     is TU elements plus one 4-byte word (one element for 8 and 16 bytes):
+//     an odd number of words, so a column read touches every bank once.
+//     64 x 64 elements up to 4 bytes, 32 x 64 for 8 and 16: 4.3, 8.4, 16.6,
+//     16.9 and 33.8 KiB of LDS, so the 160 KiB of a CDNA4 CU hold the four
+//     workgroups per CU that a grid of 1024 gives with room to spare.
+//     Patch rows do not start on 16-byte boundaries of the output in general:
+//     windows wholly inside a patch row are stored as one aligned 16-byte
+//     vector and summed with checksum_add; a row's head and tail go out
+//     element by element (naturally aligned stores of the element size) and
+//     are summed per element: the checksum is linear, so an element at byte b
+//     of the output adds value << 8 * (b % 4) to s0 and the same times the
+//     word weight to t.  Every output byte is written exactly once, by one
+//     lane; the lane that stores the last element also stores the zero
+//     padding behind it.
+//
+// Both paths end like the other checksum kernels: wave shuffles, LDS, one
+// atomicAdd pair per workgroup.  The source is only read; no byte outside
+// [dst, dst + dst_bytes) is written.  This is pure data movement: there is no
+// product to accumulate, so the matrix (MFMA) instructions have nothing to do
+// here and are not used.
+//
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): no scratch in
+// any instantiation; the figures are in profiles/strided_results.md.
+struct GatherParams {
+    const unsigned char* src;
+    unsigned char* dst;
+    unsigned long long numel;      // elements
+    unsigned long long dst_bytes;  // round_up(numel * ES, 16)
+    // direct path: the collapsed dimensions, outermost first, padded in front
+    // with size 1 / stride 0; strides in elements of the source
+    unsigned long long size[4];
+    unsigned long long stride[4];
+    // carry[i]: what the source offset gains when dimension i + 1 wraps,
+    // stride[i] - size[i + 1] * stride[i + 1] modulo 2^64
+    unsigned long long carry[3];
+    // transpose path: C is dimension 3, U the unit-stride one, R0 and R1 the
+    // other two in order; ss = source stride, os = output stride, in elements
+    unsigned long long szU, szC, ssC, osU;
+    unsigned long long szR1, ssR0, ssR1, osR0, osR1;
+    unsigned long long nU, nC, npatch;  // patches along U, along C, in all
+};
+
+template <int ES> struct GatherElem;
+template <> struct GatherElem<1> { typedef unsigned char type; };
+template <> struct GatherElem<2> { typedef unsigned short type; };
+template <> struct GatherElem<4> { typedef unsigned int type; };
+template <> struct GatherElem<8> { typedef unsigned long long type; };
+template <> struct GatherElem<16> { typedef u32x4 type; };
+
+// element k (a constant once unrolled) of a 16-byte vector
+template <int ES>
+__device__ __forceinline__ void gather_put(u32x4& v, int k,
+                                           typename GatherElem<ES>::type e) {
+    if constexpr (ES == 16) {
+        v = e;
+    } else if constexpr (ES == 8) {
+        v[2 * k] = (unsigned int)e;
+        v[2 * k + 1] = (unsigned int)(e >> 32);
+    } else if constexpr (ES == 4) {
+        v[k] = e;
+    } else {
+        v[k * ES / 4] |= (unsigned int)e << (8 * (k * ES % 4));
+    }
+}
+
+// one element of at most 8 bytes at byte offset b of the output, as the
+// words it lies in would be summed
+template <int ES>
+__device__ __forceinline__ void gather_sum_elem(unsigned long long& s0, unsigned long long& t,
+                                                typename GatherElem<ES>::type e,
+                                                unsigned long long b) {
+    const unsigned int w = (unsigned int)(b >> 2);
+    if constexpr (ES == 8) {
+        const unsigned int lo = (unsigned int)e, hi = (unsigned int)(e >> 32);
+        s0 += (unsigned long long)lo + hi;
+        t += (unsigned long long)lo * w + (unsigned long long)hi * (unsigned int)(w + 1);
+    } else {
+        const unsigned long long x = (unsigned long long)e << (8 * ((unsigned int)b & 3u));
+        s0 += x;
+        t += x * w;
+    }
+}
+
+template <int ES, typename IDX>
+__device__ __forceinline__ void gather_direct(const GatherParams& p, unsigned long long& s0,
+                                              unsigned long long& t) {
+    typedef typename GatherElem<ES>::type T;
+    constexpr int EPV = 16 / ES;  // elements per vector
+    const T* __restrict__ src = reinterpret_cast<const T*>(p.src);
+    u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(p.dst);
+    const unsigned long long nvec = p.dst_bytes / 16;
+    const unsigned long long ntiles = (nvec + kPackTileVecs - 1) / kPackTileVecs;
+    const IDX sz1 = (IDX)p.size[1], sz2 = (IDX)p.size[2], sz3 = (IDX)p.size[3];
+    for (unsigned long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+#pragma unroll
+        for (int u = 0; u < kPackUnroll; ++u) {
+            const unsigned long long vi = tile * kPackTileVecs + u * 256 + threadIdx.x;
+            if (vi >= nvec) continue;
+            const unsigned long long e0 = vi * EPV;  // < numel: the vector holds data
+            IDX r = (IDX)e0;
+            IDX c3 = r % sz3; r /= sz3;
+            IDX c2 = r % sz2; r /= sz2;
+            IDX c1 = r % sz1;
+            const IDX c0 = r / sz1;
+            unsigned long long off = (unsigned long long)c0 * p.stride[0] +
+                                     (unsigned long long)c1 * p.stride[1] +
+                                     (unsigned long long)c2 * p.stride[2] +
+                                     (unsigned long long)c3 * p.stride[3];
+            u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < EPV; ++k) {
+                if (e0 + k < p.numel) gather_put<ES>(v, k, src[off]);
+                if constexpr (EPV > 1) {  // on to the next element, with carry
+                    off += p.stride[3];
+                    if (++c3 == sz3) {
+                        c3 = 0;
+                        off += p.carry[2];
+                        if (++c2 == sz2) {
+                            c2 = 0;
+                            off += p.carry[1];
+                            if (++c1 == sz1) {
+                                c1 = 0;
+                                off += p.carry[0];
+                            }
+                        }
+                    }
+                }
+            }
+            dst[vi] = v;
+            checksum_add(s0, t, v, (unsigned int)(vi * 4));
+        }
+    }
+}
+
+template <int ES> struct GatherTile {
+    static constexpr int TU = ES <= 4 ? 64 : 32;
+    static constexpr int TC = 64;
+    static constexpr int PITCH = TU * ES + (ES < 4 ? 4 : ES);  // bytes per LDS row
+};
+
+template <int ES>
+__device__ __forceinline__ void gather_transpose(const GatherParams& p, unsigned long long& s0,
+                                                 unsigned long long& t) {
+    typedef typename GatherElem<ES>::type T;
+    constexpr int EPV = 16 / ES;
+    constexpr int TU = GatherTile<ES>::TU, TC = GatherTile<ES>::TC;
+    constexpr int PITCH = GatherTile<ES>::PITCH;
+    __shared__ __attribute__((aligned(16))) unsigned char tile[TC * PITCH];
+    const unsigned long long data_bytes = p.numel * ES;
+    for (unsigned long long patch = blockIdx.x; patch < p.npatch; patch += gridDim.x) {
+        // the patch's coordinates: wave-uniform, from the patch index alone
+        const unsigned long long pc = patch % p.nC;
+        unsigned long long r = patch / p.nC;
+        const unsigned long long pu = r % p.nU;
+        r /= p.nU;
+        const unsigned long long r1 = r % p.szR1, r0 = r / p.szR1;
+        const unsigned long long u0 = pu * TU, c0 = pc * TC;
+        const unsigned int nu = (unsigned int)(p.szU - u0 < TU ? p.szU - u0 : TU);
+        const unsigned int nc = (unsigned int)(p.szC - c0 < TC ? p.szC - c0 : TC);
+        const T* __restrict__ src = reinterpret_cast<const T*>(p.src) +
+                                    (r0 * p.ssR0 + r1 * p.ssR1 + u0 + c0 * p.ssC);
+        const unsigned long long out0 = r0 * p.osR0 + r1 * p.osR1 + u0 * p.osU + c0;
+
+        // in: lanes along U, the source's unit-stride direction
+        for (unsigned int i = threadIdx.x; i < TU * TC; i += 256) {
+            const unsigned int ul = i % TU, cl = i / TU;
+            if (ul < nu && cl < nc)
+                *reinterpret_cast<T*>(tile + cl * PITCH + ul * ES) = src[ul + cl * p.ssC];
+        }
+        __syncthreads();
+
+        // out: lanes along C.  A row of nc elements touches at most `slots`
+        // aligned 16-byte windows of the output
+        const unsigned int row_bytes = nc * ES;
+        const bool aligned = (out0 * ES) % 16 == 0 && (p.osU * ES) % 16 == 0;
+        const unsigned int slots = aligned ? (row_bytes + 15) / 16 : (row_bytes + 14) / 16 + 1;
+        for (unsigned int i = threadIdx.x; i < nu * slots; i += 256) {
+            const unsigned int ul = i / slots, s = i % slots;
+            const unsigned long long a = (out0 + ul * p.osU) * ES;  // the row's first byte
+            const unsigned long long w = (a & ~15ull) + 16ull * s;
+            const unsigned long long lo = a > w ? a : w;
+            const unsigned long long hi = a + row_bytes < w + 16 ? a + row_bytes : w + 16;
+            if (lo >= hi) continue;
+            const unsigned char* col = tile + ul * ES;
+            unsigned int cl = (unsigned int)(lo - a) / ES;
+            if (hi - lo == 16) {
+                u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int k = 0; k < EPV; ++k)
+                    gather_put<ES>(v, k, *reinterpret_cast<const T*>(col + (cl + k) * PITCH));
+                *reinterpret_cast<u32x4*>(p.dst + lo) = v;
+                checksum_add(s0, t, v, (unsigned int)(lo >> 2));
+            } else if constexpr (ES < 16) {  // a 16-byte element is always a whole window
+                for (unsigned long long b = lo; b < hi; b += ES, ++cl) {
+                    const T e = *reinterpret_cast<const T*>(col + cl * PITCH);
+                    *reinterpret_cast<T*>(p.dst + b) = e;
+                    gather_sum_elem<ES>(s0, t, e, b);
+                }
+                if (hi == data_bytes)  // the last element: its owner stores the padding
+                    for (unsigned long long b = hi; b < p.dst_bytes; b += ES)
+                        *reinterpret_cast<T*>(p.dst + b) = (T)0;
+            }
+        }
+        __syncthreads();  // the tile is free for the next patch
+    }
+}
+
+// MODE 0: direct, 32-bit element indices; 1: direct, 64-bit; 2: transpose
+template <int ES, int MODE>
+__global__ __launch_bounds__(256) void csp_gather_checksum_kernel(
+    GatherParams p, unsigned long long* __restrict__ out) {
+    unsigned long long s0 = 0, t = 0;
+    if constexpr (MODE == 0) gather_direct<ES, unsigned int>(p, s0, t);
+    else if constexpr (MODE == 1) gather_direct<ES, unsigned long long>(p, s0, t);
+    else gather_transpose<ES>(p, s0, t);
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+typedef void (*gather_fn)(GatherParams, unsigned long long*);
+
+template <int ES>
+static gather_fn gather_variant_of(int mode) {
+    if (mode == 0) return csp_gather_checksum_kernel<ES, 0>;
+    if (mode == 1) return csp_gather_checksum_kernel<ES, 1>;
+    return csp_gather_checksum_kernel<ES, 2>;
+}
+
+static gather_fn gather_variant(unsigned int es, int mode) {
+    switch (es) {
+        case 1: return gather_variant_of<1>(mode);
+        case 2: return gather_variant_of<2>(mode);
+        case 4: return gather_variant_of<4>(mode);
+        case 8: return gather_variant_of<8>(mode);
+        default: return gather_variant_of<16>(mode);
+    }
+}
+
+// The transpose path is taken when both U and C hold at least this many
+// elements: half a tile edge, so that a patch is at least a quarter full and
+// a row of the coalesced load covers 128 bytes of 4-byte elements.  Below
+// it most of a patch's LDS slots and both of its barriers serve nothing, and
+// the direct path's strided loads find their neighbours in the caches.
+// Reasoned, not measured.
+static const uint64_t kGatherTransposeMin = 32;
+
+#define CSP_GATHER_PATH_DIRECT 1     // per-element loads
+#define CSP_GATHER_PATH_DIRECT16 2   // the direct kernel on 16-byte elements
+#define CSP_GATHER_PATH_TRANSPOSE 3  // LDS tile
+
+// At most 1024 blocks, the cap of the other kernels that carry a checksum.
+static const size_t kGatherGridCapDefault = 1024;
+static size_t g_gather_grid_cap = kGatherGridCapDefault;
+static int g_gather_force_path = 0;
+
+// Tools only: the grid cap of the next csp_gather_checksum_dev calls
+// (0 restores the default).  Returns the cap in effect.  With a cap of 1, 2
+// or 3 blocks a few tiles or patches make every block loop over several.
+extern "C" size_t csp_gather_checksum_grid_cap(size_t cap) {
+    g_gather_grid_cap = cap ? std::min(cap, size_t(65536)) : kGatherGridCapDefault;
+    return g_gather_grid_cap;
+}
+
+// Tools only: 0 leaves the path of the next csp_gather_checksum_dev calls to
+// the host's choice, 1 forces the direct path, so that a test can run both
+// paths on one input.  Returns the value in effect.
+extern "C" int csp_gather_checksum_path(int force) {
+    g_gather_force_path = force == 1 ? 1 : 0;
+    return g_gather_force_path;
+}
+
+// Write the ndim-dimensional strided tensor at device pointer src (sizes and
+// strides in elements of elem_size bytes, as torch gives them) in row-major
+// order to dst and put csp_checksum_dev(dst, dst_bytes) into out[2], from the
+// same pass.  dst is 16-byte aligned, dst_bytes == round_up(numel *
+// elem_size, 16), the padding is stored as zero.  Stride 0 is valid.
+// Returns -1 with a message and launches nothing for: elem_size not in
+// {1, 2, 4, 8, 16}; ndim above 8; more than 4 dimensions after size-1
+// dimensions are dropped and contiguous neighbours merged; a null or
+// misaligned dst; src null or not aligned to elem_size; a wrong dst_bytes;
+// dst_bytes above 16 GiB; any address overflow; and a source extent
+// [src, src + (1 + sum (size_i - 1) * stride_i) * elem_size) that overlaps
+// [dst, dst + dst_bytes) (ranges that only touch are fine).  numel == 0
+// returns 0 with out = (0, 0).  *path_out (optional): which path ran, one of
+// CSP_GATHER_PATH_*, 0 when nothing was launched.  Runs on copy_stream() and
+// synchronises it before returning; a source written on another stream must
+// be complete first.  kernel_ms (optional): the kernel alone, from events
+// around the launch.
+extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsigned ndim,
+                                       const uint64_t* sizes, const uint64_t* strides,
+                                       void* dst, size_t dst_bytes, uint64_t out[2],
+                                       double* kernel_ms, int* path_out) {
+    out[0] = out[1] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (path_out) *path_out = 0;
+    if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8 &&
+        elem_size != 16) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: elem_size %u is not 1, 2, 4, 8 or 16", elem_size);
+        return -1;
+    }
+    if (ndim > 8 || (ndim > 0 && (sizes == nullptr || strides == nullptr))) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: %u dimensions (at most 8, with sizes and strides)",
+                 ndim);
+        return -1;
+    }
+    uint64_t numel = 1;
+    bool overflow = false;
+    for (unsigned i = 0; i < ndim; ++i)
+        if (sizes[i] == 0) numel = 0;
+    for (unsigned i = 0; i < ndim && numel != 0; ++i)
+        overflow |= __builtin_mul_overflow(numel, sizes[i], &numel);
+    uint64_t data_bytes = 0;
+    overflow |= __builtin_mul_overflow(numel, (uint64_t)elem_size, &data_bytes);
+    overflow |= data_bytes + 15 < data_bytes;
+    if (overflow) {
+        snprintf(g_err, sizeof(g_err), "csp_gather_checksum_dev: the element count overflows");
+        return -1;
+    }
+    if ((uint64_t)dst_bytes != ((data_bytes + 15) & ~uint64_t(15))) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: dst_bytes is %zu, %llu elements of %u bytes need %llu",
+                 dst_bytes, (unsigned long long)numel, elem_size,
+                 (unsigned long long)((data_bytes + 15) & ~uint64_t(15)));
+        return -1;
+    }
+    if (numel == 0) return 0;
+    if ((uint64_t)dst_bytes > kPackChecksumMaxBytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: dst_bytes %zu is above 16 GiB", dst_bytes);
+        return -1;
+    }
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t sa = reinterpret_cast<uintptr_t>(src);
+    if (d == 0 || d % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: dst %p is null or not 16-byte aligned", dst);
+        return -1;
+    }
+    if (sa == 0 || sa % elem_size != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: src %p is null or not aligned to %u bytes", src,
+                 elem_size);
+        return -1;
+    }
+
+    // collapse: no size-1 dimensions, contiguous neighbours merged
+    uint64_t sz[8], st[8];
+    int nd = 0;
+    for (unsigned i = 0; i < ndim; ++i) {
+        if (sizes[i] == 1) continue;
+        uint64_t run = 0;  // the stride of a neighbour that continues dimension i's rows
+        if (nd > 0 && !__builtin_mul_overflow(strides[i], sizes[i], &run) && st[nd - 1] == run) {
+            sz[nd - 1] *= sizes[i];  // within numel: cannot overflow
+            st[nd - 1] = strides[i];
+        } else {
+            sz[nd] = sizes[i];
+            st[nd] = strides[i];
+            ++nd;
+        }
+    }
+    if (nd == 0) {  // one element
+        sz[0] = 1;
+        st[0] = 1;
+        nd = 1;
+    }
+    if (nd > 4) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: %d dimensions are left after collapsing, at most 4 "
+                 "are served", nd);
+        return -1;
+    }
+    // the source extent, and its overlap with the destination
+    uint64_t extent = 1;  // elements
+    for (int i = 0; i < nd; ++i) {
+        uint64_t span = 0;
+        overflow |= __builtin_mul_overflow(sz[i] - 1, st[i], &span);
+        overflow |= __builtin_add_overflow(extent, span, &extent);
+    }
+    uint64_t extent_bytes = 0;
+    overflow |= __builtin_mul_overflow(extent, (uint64_t)elem_size, &extent_bytes);
+    if (overflow || sa + extent_bytes < sa || d + dst_bytes < d) {
+        snprintf(g_err, sizeof(g_err), "csp_gather_checksum_dev: an address range overflows");
+        return -1;
+    }
+    if (sa < d + dst_bytes && d < sa + extent_bytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_gather_checksum_dev: %llu source bytes at %p overlap %zu bytes at dst %p",
+                 (unsigned long long)extent_bytes, src, dst_bytes, dst);
+        return -1;
+    }
+
+    GatherParams p = {};
+    p.src = static_cast<const unsigned char*>(src);
+    p.dst = static_cast<unsigned char*>(dst);
+    p.dst_bytes = dst_bytes;
+    unsigned int es = elem_size;
+    int mode = 0, path = CSP_GATHER_PATH_DIRECT;
+    size_t work = 0;  // tiles or patches
+    const int unit = [&] {  // U: a dimension other than C with source stride 1
+        for (int i = 0; i < nd - 1; ++i)
+            if (st[i] == 1 && sz[i] >= kGatherTransposeMin) return i;
+        return -1;
+    }();
+    if (g_gather_force_path != 1 && nd >= 2 && st[nd - 1] != 1 &&
+        sz[nd - 1] >= kGatherTransposeMin && unit >= 0) {
+        mode = 2;
+        path = CSP_GATHER_PATH_TRANSPOSE;
+        p.numel = numel;
+        uint64_t os[4];  // output strides: row-major
+        os[nd - 1] = 1;
+        for (int i = nd - 2; i >= 0; --i) os[i] = os[i + 1] * sz[i + 1];
+        p.szU = sz[unit];
+        p.osU = os[unit];
+        p.szC = sz[nd - 1];
+        p.ssC = st[nd - 1];
+        p.szR1 = 1;  // R0's size is not needed: it is what is left of the patch index
+        int rest = 0;
+        for (int i = nd - 2; i >= 0; --i) {  // the other dimensions, innermost first
+            if (i == unit) continue;
+            if (rest == 0) { p.szR1 = sz[i]; p.ssR1 = st[i]; p.osR1 = os[i]; }
+            else { p.ssR0 = st[i]; p.osR0 = os[i]; }
+            ++rest;
+        }
+        const uint64_t tu = es <= 4 ? 64 : 32, tc = 64;
+        p.nU = (p.szU + tu - 1) / tu;
+        p.nC = (p.szC + tc - 1) / tc;
+        p.npatch = (numel / (p.szU * p.szC)) * p.nU * p.nC;  // <= numel
+        work = (size_t)p.npatch;
+    } else {
+        // 16-byte sub-path: the same tensor in 16-byte elements
+        bool wide = es < 16 && st[nd - 1] == 1 && (sz[nd - 1] * es) % 16 == 0 && sa % 16 == 0;
+        for (int i = 0; wide && i < nd - 1; ++i) wide = (st[i] * es) % 16 == 0;
+        if (wide) {
+            const uint64_t per = 16 / es;
+            sz[nd - 1] /= per;
+            for (int i = 0; i < nd - 1; ++i) st[i] /= per;
+            numel /= per;
+            es = 16;
+            path = CSP_GATHER_PATH_DIRECT16;
+        }
+        mode = numel < (uint64_t(1) << 32) ? 0 : 1;
+        p.numel = numel;
+        for (int i = 0; i < 4; ++i) {
+            const int j = i - (4 - nd);
+            p.size[i] = j >= 0 ? sz[j] : 1;
+            p.stride[i] = j >= 0 ? st[j] : 0;
+        }
+        for (int i = 0; i < 3; ++i)
+            p.carry[i] = p.stride[i] - p.size[i + 1] * p.stride[i + 1];
+        work = (dst_bytes + kPackTileBytes - 1) / kPackTileBytes;
+    }
+
+    // one accumulator pair per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static int acc_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (acc == nullptr || acc_device != device) {
+        if (acc) (void)hipFree(acc);
+        acc = nullptr;
+        HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+        acc_device = device;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define GATHER_TRY(expr)                                           \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    GATHER_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t blocks = std::min(work, g_gather_grid_cap);
+    if (t0) GATHER_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(gather_variant(es, mode), dim3((unsigned int)blocks), dim3(256), 0, s,
+                       p, acc);
+    GATHER_TRY(hipGetLastError());
+    if (t1) GATHER_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    GATHER_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    GATHER_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        GATHER_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef GATHER_TRY
+    out[0] = host[0];
+    out[1] = host[1];
+    if (path_out) *path_out = path;
+    return done(0);
+}
+
 // On-box variant exploration for the HBM sweep (tools only; the probe
 // uses g_sweep_variant).  Returns measured GB/s via *gbps.
 extern "C" int csp_hbm_bench(int device, int variant, size_t bytes, int reps,

@@ -73,6 +73,7 @@ def render_worker(
     arg_cache_bytes: int = 0,
     retain_min_bytes: Optional[int] = None,
     delta_max_fraction: Optional[float] = None,
+    gather_results: bool = False,
 ) -> str:
     """Return the persistent worker script text (one per endpoint; the
     GPU slot arrives via the CSP_GPU_SLOT env var at launch).  With
@@ -89,7 +90,9 @@ def render_worker(
     ``delta_max_fraction`` (``delta_tensor_results``; ``None`` is off) is the
     executor's ``patch_args_max_fraction``: a CUDA result buffer of which at
     most that share of the blocks differs from the cached argument of the
-    same size leaves as a block delta."""
+    same size leaves as a block delta.  ``gather_results``
+    (``gather_tensor_results``) makes the worker lay out large non-contiguous
+    CUDA results with csp_gather_checksum_dev in place of ``contiguous()``."""
     text = _template_text(str(_WORKER_TEMPLATE_PATH))
     thr = DEFAULT_STAGING_THRESHOLD if staging_threshold is None else int(staging_threshold)
     replacements = {
@@ -108,6 +111,7 @@ def render_worker(
         "__CSP_DELTA_MAX_FRACTION__": repr(
             -1.0 if delta_max_fraction is None else float(delta_max_fraction)
         ),
+        "__CSP_GATHER_RESULTS__": repr(bool(gather_results)),
     }
     for token, value in replacements.items():
         text = text.replace(token, value)

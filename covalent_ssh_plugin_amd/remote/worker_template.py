@@ -108,7 +108,15 @@ Protocol (all frames: 8-byte big-endian length + payload):
              to something held: the key of a "ref", the base of a "patch" or
              a "rebase" (whose delta may then be empty).  A buffer that
              cannot be retained takes the path above and
-             meta["staging"]["retain_fallback"] says why.  A zero-length
+             meta["staging"]["retain_fallback"] says why.  With the
+             executor option gather_tensor_results a large CUDA tensor that
+             is not contiguous is laid out by ONE csp_gather_checksum_dev
+             call, into the new master (with its checksum) or into the
+             buffer its frame is streamed from, in place of torch's
+             contiguous(); the frames and their meta are the same bytes
+             either way, meta["staging"] counts "gathered_tensors" and
+             "gathered_bytes", and a tensor the kernel refuses takes
+             contiguous() with the reason in "gather_fallback".  A zero-length
              request frame means: shut down.
 
 The worker's REAL stdout is reserved for the protocol; fd 1 is
@@ -148,6 +156,9 @@ RETAIN_MIN_BYTES = int(__CSP_RETAIN_MIN_BYTES__)
 # negative = off.
 DELTA_MAX_FRACTION = float(__CSP_DELTA_MAX_FRACTION__)
 DELTA_BLOCK = 4096  # csp_diff_block_bytes()
+# Lay out a large non-contiguous CUDA result with csp_gather_checksum_dev in
+# place of torch's contiguous() (executor option gather_tensor_results).
+GATHER_RESULTS = bool(__CSP_GATHER_RESULTS__)
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
 # break the children) and every electron executes in a freshly forked
@@ -325,6 +336,20 @@ def _load_gpu_lib():
             ctypes.POINTER(ctypes.c_uint64),
             ctypes.POINTER(ctypes.c_float),
         ]
+    if GATHER_RESULTS and hasattr(lib, "csp_gather_checksum_dev"):
+        lib.csp_gather_checksum_dev.restype = ctypes.c_int
+        lib.csp_gather_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_uint,
+            ctypes.c_uint,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_double),
+            ctypes.POINTER(ctypes.c_int),
+        ]
     lib.csp_patch_unpack_checksum_dev.restype = ctypes.c_int
     lib.csp_patch_unpack_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -465,8 +490,49 @@ def _pack_checksum(lib, src_ptrs, offsets, sizes, arena_ptr, total):
     return [int(out[0]), int(out[1])]
 
 
+def _gathers(lib, t):
+    """Whether the non-contiguous CUDA tensor ``t`` is laid out by
+    csp_gather_checksum_dev (option on, symbol there, plain strided bytes)."""
+    return (
+        GATHER_RESULTS
+        and hasattr(lib, "csp_gather_checksum_dev")
+        and not t.is_contiguous()
+        and not t.is_conj()
+        and not t.is_neg()
+    )
+
+
+def _gather_into(lib, t, dst_ptr, total, stats):
+    """ONE csp_gather_checksum_dev call: the strided CUDA tensor ``t`` in
+    row-major order at ``dst_ptr`` (``total`` bytes, the data rounded up to
+    16).  Returns [s0, s1] of those bytes, or None with the reason in
+    stats["gather_fallback"]: a gather never fails a task.  The caller has
+    synchronised the null stream."""
+    import ctypes
+
+    try:
+        dims = t.dim()
+        out = (ctypes.c_uint64 * 2)()
+        rc = lib.csp_gather_checksum_dev(
+            ctypes.c_void_p(t.data_ptr()), t.element_size(), dims,
+            (ctypes.c_uint64 * dims)(*t.shape), (ctypes.c_uint64 * dims)(*t.stride()),
+            ctypes.c_void_p(dst_ptr), total, out, None, None,
+        )
+        if rc != 0:
+            raise RuntimeError(
+                "csp_gather_checksum_dev failed (rc=%d): %s"
+                % (rc, lib.csp_last_error().decode(errors="replace"))
+            )
+    except Exception as e:  # noqa: BLE001
+        stats["gather_fallback"] = repr(e)[:500]
+        return None
+    stats["gathered_tensors"] = stats.get("gathered_tensors", 0) + 1
+    stats["gathered_bytes"] = stats.get("gathered_bytes", 0) + t.numel() * t.element_size()
+    return [int(out[0]), int(out[1])]
+
+
 def _retain_buffer(lib, retain, index, src_ptrs, offsets, sizes, total, nbytes, stats,
-                   keep=True):
+                   keep=True, gather=None):
     """Result buffer ``index`` gathered, copied and checksummed by one
     csp_pack_checksum_dev call into a buffer of its own of ``total`` bytes,
     which with ``keep`` is a new argument master held under the worker's name
@@ -474,7 +540,11 @@ def _retain_buffer(lib, retain, index, src_ptrs, offsets, sizes, total, nbytes, 
     name or None).  No room in the budget, no HBM, or any refusal or error of
     the call: None, the reason in stats["retain_fallback"], and the buffer
     takes the path it takes without retention.  The caller has synchronised
-    the null stream."""
+    the null stream.
+
+    ``gather`` (gather_tensor_results): the one strided tensor that makes up
+    the buffer; ONE csp_gather_checksum_dev call fills the buffer from it, and
+    only when that is refused does torch lay it out for the pack kernel."""
     global _arg_cache_resident
     import torch
 
@@ -493,7 +563,18 @@ def _retain_buffer(lib, retain, index, src_ptrs, offsets, sizes, total, nbytes, 
                 )
         else:
             arena = torch.empty(total, dtype=torch.uint8, device="cuda")
-        sums = _pack_checksum(lib, src_ptrs, offsets, sizes, arena.data_ptr(), total)
+        sums = None
+        if gather is not None:
+            sums = _gather_into(lib, gather, arena.data_ptr(), total, stats)
+            if sums is None:
+                # refused, and stats["gather_fallback"] says why: from here on
+                # it is the path without the option, and a failure of it (no
+                # room for torch's copy) is a retention failure like any other
+                flat = gather.contiguous()
+                torch.cuda.synchronize()
+                src_ptrs = [flat.data_ptr()]
+        if sums is None:
+            sums = _pack_checksum(lib, src_ptrs, offsets, sizes, arena.data_ptr(), total)
     except Exception as e:  # noqa: BLE001 - retention never fails a task
         stats["retain_fallback"] = repr(e)[:500]
         if keep:
@@ -700,13 +781,14 @@ def _stage_result(result, stats, buffers, buffer_meta, retain=None):
         """The marker of ``t``'s retained buffer, or None."""
         if id(t) in retained_markers:
             return retained_markers[id(t)]
-        src_t = t.contiguous()
+        strided = _gathers(lib, t)
+        src_t = t if strided else t.contiguous()
         # the library's copy stream does not wait on the null stream
         torch.cuda.synchronize()
         total = (nbytes + 15) // 16 * 16
         kept = _retain_buffer(
             lib, retain, len(buffers), [src_t.data_ptr()], [0], [nbytes], total, nbytes,
-            stats,
+            stats, gather=t if strided else None,
         )
         if kept is None:
             return None
@@ -720,6 +802,21 @@ def _stage_result(result, stats, buffers, buffer_meta, retain=None):
         buffer_meta[-1]["retained"] = name
         retained_markers[id(t)] = marker
         return marker
+
+    def gather_large(t, nbytes):
+        """``t``'s bytes in row-major order in a new device buffer, filled by
+        one gather call in place of contiguous(); None when that is refused
+        or there is no room (the reason in stats["gather_fallback"])."""
+        try:
+            total = (nbytes + 15) // 16 * 16
+            flat = torch.empty(total, dtype=torch.uint8, device="cuda")
+        except Exception as e:  # noqa: BLE001 - a gather never fails a task
+            stats["gather_fallback"] = repr(e)[:500]
+            return None
+        torch.cuda.synchronize()
+        if _gather_into(lib, t, flat.data_ptr(), total, stats) is None:
+            return None
+        return flat
 
     def to_host(t):
         stats["tensors"] += 1
@@ -739,13 +836,15 @@ def _stage_result(result, stats, buffers, buffer_meta, retain=None):
                     "CUDA tensor result but the CDNA4 staging library is "
                     "not available on this GPU host"
                 )
-            src_t = t.contiguous()
+            src_t = gather_large(t, nbytes) if _gathers(lib, t) else None
+            if src_t is None:
+                src_t = t.contiguous()
             # the library's copy stream does not wait on the null stream
             torch.cuda.synchronize()
             view = _DeferredCuda(lib, src_t.data_ptr(), nbytes)
             stats["pinned_tensors"] += 1
             stats["mode"] = "pinned"
-            return emit_buffer(view, src_t, src_t.dtype, src_t.shape)
+            return emit_buffer(view, src_t, t.dtype, t.shape)
         # large CPU tensor: zero-copy out-of-band (keep tensor alive)
         src_t = t.contiguous()
         view = (ctypes.c_char * nbytes).from_address(src_t.data_ptr())

@@ -189,6 +189,13 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # holds and verifies the whole buffer.  For iterative electrons that hand
     # back most of their state unchanged.
     "delta_tensor_results": False,
+    # A large CUDA result that is not contiguous (a transpose, a permute, a
+    # column slice, channels_last, a strided subsample) is laid out by the
+    # library's own gather kernel in ONE pass, straight into the retained
+    # master (with its checksum) or into the buffer its frame is streamed
+    # from, where torch's contiguous() costs a second full-size allocation and
+    # a second read and write.  The wire format does not change.
+    "gather_tensor_results": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -392,6 +399,7 @@ class SSHExecutor(RemoteExecutor):
         rebase_tensor_args: Optional[bool] = None,
         retain_tensor_results: Optional[bool] = None,
         delta_tensor_results: Optional[bool] = None,
+        gather_tensor_results: Optional[bool] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -543,6 +551,9 @@ class SSHExecutor(RemoteExecutor):
                 "sent as a delta against an argument master in the worker's "
                 "argument cache"
             )
+        self.gather_tensor_results = bool(
+            _conf("gather_tensor_results", gather_tensor_results, default=False)
+        )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -1039,6 +1050,7 @@ class SSHExecutor(RemoteExecutor):
             delta_max_fraction=(
                 self.patch_args_max_fraction if self.delta_tensor_results else None
             ),
+            gather_results=self.gather_tensor_results,
         )
         digest = _script_digest(text)
         key = self._pool_key()
