@@ -28,6 +28,10 @@ gfx950 only) provides:
 * ``csp_gather_checksum_dev`` — one strided device tensor written in
   row-major order to a contiguous buffer, with that buffer's checksum from the
   same launch (``gather_tensor_results``),
+* ``csp_pack_gather_checksum_dev`` — the packed arena filled from contiguous
+  and strided tensors together by one launch, with its checksum
+  (``pack_tensor_results`` with ``gather_tensor_results``), and
+  ``csp_gather_supported``, the host-side question whether a layout is served,
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
   ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
@@ -51,6 +55,22 @@ _lib: Optional[ctypes.CDLL] = None
 
 class GpuLibError(RuntimeError):
     """The CDNA4 GPU extension is missing or a call into it failed."""
+
+
+class PackGatherSeg(ctypes.Structure):
+    """``CspPackGatherSeg``: one segment of ``csp_pack_gather_checksum_dev``.
+    ``ndim == 0`` is ``nbytes`` contiguous bytes; otherwise a strided tensor
+    with ``shape`` and ``stride`` in elements, as torch reports them."""
+
+    _fields_ = [
+        ("src", ctypes.c_void_p),
+        ("dst_off", ctypes.c_uint64),
+        ("nbytes", ctypes.c_uint64),
+        ("elem_size", ctypes.c_uint32),
+        ("ndim", ctypes.c_uint32),
+        ("shape", ctypes.c_uint64 * 8),
+        ("stride", ctypes.c_uint64 * 8),
+    ]
 
 
 def local_gpu_lib_path() -> str:
@@ -243,6 +263,27 @@ def load(path: str = "") -> ctypes.CDLL:
     lib.csp_gather_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_gather_checksum_path.restype = ctypes.c_int
     lib.csp_gather_checksum_path.argtypes = [ctypes.c_int]
+    lib.csp_pack_gather_checksum_dev.restype = ctypes.c_int
+    lib.csp_pack_gather_checksum_dev.argtypes = [
+        ctypes.POINTER(PackGatherSeg),
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_int),
+    ]
+    lib.csp_gather_supported.restype = ctypes.c_int
+    lib.csp_gather_supported.argtypes = [
+        ctypes.c_uint,
+        ctypes.c_uint,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+    ]
+    lib.csp_pack_gather_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_pack_gather_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_pack_gather_checksum_path.restype = ctypes.c_int
+    lib.csp_pack_gather_checksum_path.argtypes = [ctypes.c_int]
     lib.csp_mem_info.restype = ctypes.c_int
     lib.csp_mem_info.argtypes = [
         ctypes.c_int,
@@ -737,6 +778,90 @@ def gather_checksum_path(force: int = 0) -> int:
     """Tools only: 1 forces the direct path of :func:`gather_checksum_device`,
     0 restores the host's choice.  Returns the value in effect."""
     return int(load().csp_gather_checksum_path(int(force)))
+
+
+PACK_GATHER_PATHS = dict(GATHER_PATHS)
+PACK_GATHER_PATHS[4] = "copy"
+
+
+def pack_gather_segments(segments):
+    """A ``PackGatherSeg`` array from ``(src_ptr, dst_off, nbytes)`` tuples
+    (contiguous bytes) and ``(src_ptr, dst_off, nbytes, elem_size, shape,
+    stride)`` tuples (strided tensors)."""
+    array = (PackGatherSeg * len(segments))()
+    for seg, entry in zip(array, segments):
+        seg.src = int(entry[0]) or None
+        seg.dst_off, seg.nbytes = int(entry[1]), int(entry[2])
+        if len(entry) > 3:
+            seg.elem_size, shape, stride = int(entry[3]), entry[4], entry[5]
+            seg.ndim = len(shape)
+            if len(shape) > 8 or len(stride) != len(shape):
+                raise GpuLibError("a packed strided segment has at most 8 dimensions")
+            seg.shape[: len(shape)] = [int(v) for v in shape]
+            seg.stride[: len(stride)] = [int(v) for v in stride]
+    return array
+
+
+def pack_gather_checksum_device(segments, arena_ptr: int, arena_bytes: int) -> dict:
+    """:func:`pack_checksum_device` for a mix of contiguous and strided
+    sources in ONE kernel launch (``pack_tensor_results`` with
+    ``gather_tensor_results``).  ``segments`` is a sequence of ``(src_ptr,
+    dst_off, nbytes)`` for contiguous bytes and ``(src_ptr, dst_off, nbytes,
+    elem_size, shape, stride)`` for a strided tensor, which lands in row-major
+    order; offsets follow :func:`pack_layout`.  Returns ``{"sums": (s0, s1),
+    "kernel_ms", "paths"}``: ``sums`` equals ``checksum_device(arena_ptr,
+    arena_bytes)``, ``paths`` has one of ``"copy"``, ``"direct"``,
+    ``"direct16"``, ``"transpose"`` or ``"none"`` (no byte) per segment.
+    Refuses what :func:`pack_checksum_device` refuses, a strided segment that
+    :func:`gather_supported` does not serve, an ``nbytes`` that disagrees with
+    the shape, and a source extent that overlaps the arena (``GpuLibError``
+    naming the segment, nothing launched).  Runs on the library's copy stream;
+    sources written on another stream must be complete first."""
+    lib = load()
+    n = len(segments)
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    paths = (ctypes.c_int * max(n, 1))()
+    _check(
+        lib,
+        lib.csp_pack_gather_checksum_dev(
+            pack_gather_segments(segments), n, ctypes.c_void_p(arena_ptr or None), arena_bytes,
+            out, ctypes.byref(kernel_ms), paths,
+        ),
+        "csp_pack_gather_checksum_dev",
+    )
+    return {
+        "sums": (int(out[0]), int(out[1])),
+        "kernel_ms": kernel_ms.value,
+        "paths": [PACK_GATHER_PATHS[paths[k]] for k in range(n)],
+    }
+
+
+def gather_supported(elem_size: int, sizes, strides) -> bool:
+    """Whether :func:`pack_gather_checksum_device` serves a strided segment of
+    this layout: element size 1, 2, 4, 8 or 16, at most 4 dimensions after
+    collapsing, fewer than 2^32 elements.  Host only, nothing is launched."""
+    n = len(sizes)
+    if n > 8 or len(strides) != n:
+        return False
+    return bool(load().csp_gather_supported(
+        elem_size, n,
+        (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in sizes]),
+        (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in strides]),
+    ))
+
+
+def pack_gather_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`pack_gather_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_pack_gather_checksum_grid_cap(int(cap)))
+
+
+def pack_gather_checksum_path(force: int = 0) -> int:
+    """Tools only: 1 makes :func:`pack_gather_checksum_device` take the direct
+    path where the host would choose the transpose, 0 restores the host's
+    choice.  Returns the value in effect."""
+    return int(load().csp_pack_gather_checksum_path(int(force)))
 
 
 def staged_d2h_bytes(data_ptr: int, nbytes: int) -> bytes:

@@ -93,6 +93,7 @@
 #include <ctime>
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include <utility>
 
@@ -3116,17 +3117,24 @@ __device__ __forceinline__ void gather_sum_elem(unsigned long long& s0, unsigned
     }
 }
 
-template <int ES, typename IDX>
-__device__ __forceinline__ void gather_direct(const GatherParams& p, unsigned long long& s0,
+// Tiles first, first + step, ... below last of the direct path's output.
+// word_base: the index of dst's first word in what is summed (0 when dst is
+// the whole of it).  TABLE: p comes out of a table in memory, so the source
+// is declared global (see CSP_GLOBAL); a kernel argument needs no telling.
+template <int ES, typename IDX, bool TABLE = false>
+__device__ __forceinline__ void gather_direct(const GatherParams& p, unsigned long long first,
+                                              unsigned long long step, unsigned long long last,
+                                              unsigned int word_base, unsigned long long& s0,
                                               unsigned long long& t) {
     typedef typename GatherElem<ES>::type T;
+    typedef typename std::conditional<TABLE, const CSP_GLOBAL T*, const T*>::type src_t;
+    typedef typename std::conditional<TABLE, CSP_GLOBAL u32x4*, u32x4*>::type dst_t;
     constexpr int EPV = 16 / ES;  // elements per vector
-    const T* __restrict__ src = reinterpret_cast<const T*>(p.src);
-    u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(p.dst);
+    const src_t __restrict__ src = (src_t)p.src;
+    const dst_t __restrict__ dst = (dst_t)p.dst;
     const unsigned long long nvec = p.dst_bytes / 16;
-    const unsigned long long ntiles = (nvec + kPackTileVecs - 1) / kPackTileVecs;
     const IDX sz1 = (IDX)p.size[1], sz2 = (IDX)p.size[2], sz3 = (IDX)p.size[3];
-    for (unsigned long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    for (unsigned long long tile = first; tile < last; tile += step) {
 #pragma unroll
         for (int u = 0; u < kPackUnroll; ++u) {
             const unsigned long long vi = tile * kPackTileVecs + u * 256 + threadIdx.x;
@@ -3162,7 +3170,7 @@ __device__ __forceinline__ void gather_direct(const GatherParams& p, unsigned lo
                 }
             }
             dst[vi] = v;
-            checksum_add(s0, t, v, (unsigned int)(vi * 4));
+            checksum_add(s0, t, v, word_base + (unsigned int)(vi * 4));
         }
     }
 }
@@ -3173,71 +3181,86 @@ template <int ES> struct GatherTile {
     static constexpr int PITCH = TU * ES + (ES < 4 ? 4 : ES);  // bytes per LDS row
 };
 
+// One patch of the transpose path through `tile` (TC * PITCH bytes of LDS,
+// 16-byte aligned), which is free again when this returns.  base: the byte
+// offset of dst in what is summed (0 when dst is the whole of it, else a
+// multiple of 16).
 template <int ES>
-__device__ __forceinline__ void gather_transpose(const GatherParams& p, unsigned long long& s0,
-                                                 unsigned long long& t) {
+__device__ __forceinline__ void gather_transpose_patch(const GatherParams& p,
+                                                       unsigned char* tile,
+                                                       unsigned long long patch,
+                                                       unsigned long long base,
+                                                       unsigned long long& s0,
+                                                       unsigned long long& t) {
     typedef typename GatherElem<ES>::type T;
     constexpr int EPV = 16 / ES;
     constexpr int TU = GatherTile<ES>::TU, TC = GatherTile<ES>::TC;
     constexpr int PITCH = GatherTile<ES>::PITCH;
-    __shared__ __attribute__((aligned(16))) unsigned char tile[TC * PITCH];
     const unsigned long long data_bytes = p.numel * ES;
-    for (unsigned long long patch = blockIdx.x; patch < p.npatch; patch += gridDim.x) {
-        // the patch's coordinates: wave-uniform, from the patch index alone
-        const unsigned long long pc = patch % p.nC;
-        unsigned long long r = patch / p.nC;
-        const unsigned long long pu = r % p.nU;
-        r /= p.nU;
-        const unsigned long long r1 = r % p.szR1, r0 = r / p.szR1;
-        const unsigned long long u0 = pu * TU, c0 = pc * TC;
-        const unsigned int nu = (unsigned int)(p.szU - u0 < TU ? p.szU - u0 : TU);
-        const unsigned int nc = (unsigned int)(p.szC - c0 < TC ? p.szC - c0 : TC);
-        const T* __restrict__ src = reinterpret_cast<const T*>(p.src) +
-                                    (r0 * p.ssR0 + r1 * p.ssR1 + u0 + c0 * p.ssC);
-        const unsigned long long out0 = r0 * p.osR0 + r1 * p.osR1 + u0 * p.osU + c0;
+    // the patch's coordinates: wave-uniform, from the patch index alone
+    const unsigned long long pc = patch % p.nC;
+    unsigned long long r = patch / p.nC;
+    const unsigned long long pu = r % p.nU;
+    r /= p.nU;
+    const unsigned long long r1 = r % p.szR1, r0 = r / p.szR1;
+    const unsigned long long u0 = pu * TU, c0 = pc * TC;
+    const unsigned int nu = (unsigned int)(p.szU - u0 < TU ? p.szU - u0 : TU);
+    const unsigned int nc = (unsigned int)(p.szC - c0 < TC ? p.szC - c0 : TC);
+    const CSP_GLOBAL T* __restrict__ src =
+        (const CSP_GLOBAL T*)p.src + (r0 * p.ssR0 + r1 * p.ssR1 + u0 + c0 * p.ssC);
+    CSP_GLOBAL unsigned char* const dst = (CSP_GLOBAL unsigned char*)p.dst;
+    const unsigned long long out0 = r0 * p.osR0 + r1 * p.osR1 + u0 * p.osU + c0;
 
-        // in: lanes along U, the source's unit-stride direction
-        for (unsigned int i = threadIdx.x; i < TU * TC; i += 256) {
-            const unsigned int ul = i % TU, cl = i / TU;
-            if (ul < nu && cl < nc)
-                *reinterpret_cast<T*>(tile + cl * PITCH + ul * ES) = src[ul + cl * p.ssC];
-        }
-        __syncthreads();
-
-        // out: lanes along C.  A row of nc elements touches at most `slots`
-        // aligned 16-byte windows of the output
-        const unsigned int row_bytes = nc * ES;
-        const bool aligned = (out0 * ES) % 16 == 0 && (p.osU * ES) % 16 == 0;
-        const unsigned int slots = aligned ? (row_bytes + 15) / 16 : (row_bytes + 14) / 16 + 1;
-        for (unsigned int i = threadIdx.x; i < nu * slots; i += 256) {
-            const unsigned int ul = i / slots, s = i % slots;
-            const unsigned long long a = (out0 + ul * p.osU) * ES;  // the row's first byte
-            const unsigned long long w = (a & ~15ull) + 16ull * s;
-            const unsigned long long lo = a > w ? a : w;
-            const unsigned long long hi = a + row_bytes < w + 16 ? a + row_bytes : w + 16;
-            if (lo >= hi) continue;
-            const unsigned char* col = tile + ul * ES;
-            unsigned int cl = (unsigned int)(lo - a) / ES;
-            if (hi - lo == 16) {
-                u32x4 v = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int k = 0; k < EPV; ++k)
-                    gather_put<ES>(v, k, *reinterpret_cast<const T*>(col + (cl + k) * PITCH));
-                *reinterpret_cast<u32x4*>(p.dst + lo) = v;
-                checksum_add(s0, t, v, (unsigned int)(lo >> 2));
-            } else if constexpr (ES < 16) {  // a 16-byte element is always a whole window
-                for (unsigned long long b = lo; b < hi; b += ES, ++cl) {
-                    const T e = *reinterpret_cast<const T*>(col + cl * PITCH);
-                    *reinterpret_cast<T*>(p.dst + b) = e;
-                    gather_sum_elem<ES>(s0, t, e, b);
-                }
-                if (hi == data_bytes)  // the last element: its owner stores the padding
-                    for (unsigned long long b = hi; b < p.dst_bytes; b += ES)
-                        *reinterpret_cast<T*>(p.dst + b) = (T)0;
-            }
-        }
-        __syncthreads();  // the tile is free for the next patch
+    // in: lanes along U, the source's unit-stride direction
+    for (unsigned int i = threadIdx.x; i < TU * TC; i += 256) {
+        const unsigned int ul = i % TU, cl = i / TU;
+        if (ul < nu && cl < nc)
+            *reinterpret_cast<T*>(tile + cl * PITCH + ul * ES) = src[ul + cl * p.ssC];
     }
+    __syncthreads();
+
+    // out: lanes along C.  A row of nc elements touches at most `slots`
+    // aligned 16-byte windows of the output
+    const unsigned int row_bytes = nc * ES;
+    const bool aligned = (out0 * ES) % 16 == 0 && (p.osU * ES) % 16 == 0;
+    const unsigned int slots = aligned ? (row_bytes + 15) / 16 : (row_bytes + 14) / 16 + 1;
+    for (unsigned int i = threadIdx.x; i < nu * slots; i += 256) {
+        const unsigned int ul = i / slots, s = i % slots;
+        const unsigned long long a = (out0 + ul * p.osU) * ES;  // the row's first byte
+        const unsigned long long w = (a & ~15ull) + 16ull * s;
+        const unsigned long long lo = a > w ? a : w;
+        const unsigned long long hi = a + row_bytes < w + 16 ? a + row_bytes : w + 16;
+        if (lo >= hi) continue;
+        const unsigned char* col = tile + ul * ES;
+        unsigned int cl = (unsigned int)(lo - a) / ES;
+        if (hi - lo == 16) {
+            u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < EPV; ++k)
+                gather_put<ES>(v, k, *reinterpret_cast<const T*>(col + (cl + k) * PITCH));
+            *(CSP_GLOBAL u32x4*)(dst + lo) = v;
+            checksum_add(s0, t, v, (unsigned int)((base + lo) >> 2));
+        } else if constexpr (ES < 16) {  // a 16-byte element is always a whole window
+            for (unsigned long long b = lo; b < hi; b += ES, ++cl) {
+                const T e = *reinterpret_cast<const T*>(col + cl * PITCH);
+                *(CSP_GLOBAL T*)(dst + b) = e;
+                gather_sum_elem<ES>(s0, t, e, base + b);
+            }
+            if (hi == data_bytes)  // the last element: its owner stores the padding
+                for (unsigned long long b = hi; b < p.dst_bytes; b += ES)
+                    *(CSP_GLOBAL T*)(dst + b) = (T)0;
+        }
+    }
+    __syncthreads();  // the tile is free for the next patch
+}
+
+template <int ES>
+__device__ __forceinline__ void gather_transpose(const GatherParams& p, unsigned long long& s0,
+                                                 unsigned long long& t) {
+    __shared__ __attribute__((aligned(16))) unsigned char
+        tile[GatherTile<ES>::TC * GatherTile<ES>::PITCH];
+    for (unsigned long long patch = blockIdx.x; patch < p.npatch; patch += gridDim.x)
+        gather_transpose_patch<ES>(p, tile, patch, 0ull, s0, t);
 }
 
 // MODE 0: direct, 32-bit element indices; 1: direct, 64-bit; 2: transpose
@@ -3245,8 +3268,12 @@ template <int ES, int MODE>
 __global__ __launch_bounds__(256) void csp_gather_checksum_kernel(
     GatherParams p, unsigned long long* __restrict__ out) {
     unsigned long long s0 = 0, t = 0;
-    if constexpr (MODE == 0) gather_direct<ES, unsigned int>(p, s0, t);
-    else if constexpr (MODE == 1) gather_direct<ES, unsigned long long>(p, s0, t);
+    // the direct path's 16 KiB tiles of the output
+    const unsigned long long ntiles = (p.dst_bytes / 16 + kPackTileVecs - 1) / kPackTileVecs;
+    if constexpr (MODE == 0)
+        gather_direct<ES, unsigned int>(p, blockIdx.x, gridDim.x, ntiles, 0u, s0, t);
+    else if constexpr (MODE == 1)
+        gather_direct<ES, unsigned long long>(p, blockIdx.x, gridDim.x, ntiles, 0u, s0, t);
     else gather_transpose<ES>(p, s0, t);
     unsigned long long s1 = t + s0;
 
@@ -3319,6 +3346,149 @@ extern "C" int csp_gather_checksum_path(int force) {
     return g_gather_force_path;
 }
 
+// The host side that csp_gather_checksum_dev and csp_pack_gather_checksum_dev
+// share.  None of these runs device code; `who` opens the message in g_err.
+
+// Element count and data bytes of a strided tensor; false with a message for
+// an element size outside 1, 2, 4, 8, 16, more than 8 dimensions, or overflow.
+static bool gather_count(const char* who, unsigned elem_size, unsigned ndim,
+                         const uint64_t* sizes, const uint64_t* strides, uint64_t* numel_out,
+                         uint64_t* data_bytes_out) {
+    if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8 &&
+        elem_size != 16) {
+        snprintf(g_err, sizeof(g_err), "%s: elem_size %u is not 1, 2, 4, 8 or 16", who,
+                 elem_size);
+        return false;
+    }
+    if (ndim > 8 || (ndim > 0 && (sizes == nullptr || strides == nullptr))) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: %u dimensions (at most 8, with sizes and strides)", who, ndim);
+        return false;
+    }
+    uint64_t numel = 1;
+    bool overflow = false;
+    for (unsigned i = 0; i < ndim; ++i)
+        if (sizes[i] == 0) numel = 0;
+    for (unsigned i = 0; i < ndim && numel != 0; ++i)
+        overflow |= __builtin_mul_overflow(numel, sizes[i], &numel);
+    uint64_t data_bytes = 0;
+    overflow |= __builtin_mul_overflow(numel, (uint64_t)elem_size, &data_bytes);
+    overflow |= data_bytes + 15 < data_bytes;
+    if (overflow) {
+        snprintf(g_err, sizeof(g_err), "%s: the element count overflows", who);
+        return false;
+    }
+    *numel_out = numel;
+    *data_bytes_out = data_bytes;
+    return true;
+}
+
+// The collapse rule: no size-1 dimensions, contiguous neighbours merged.
+// Returns how many dimensions are left (1 to 8).
+static int gather_collapse(unsigned ndim, const uint64_t* sizes, const uint64_t* strides,
+                           uint64_t sz[8], uint64_t st[8]) {
+    int nd = 0;
+    for (unsigned i = 0; i < ndim; ++i) {
+        if (sizes[i] == 1) continue;
+        uint64_t run = 0;  // the stride of a neighbour that continues dimension i's rows
+        if (nd > 0 && !__builtin_mul_overflow(strides[i], sizes[i], &run) && st[nd - 1] == run) {
+            sz[nd - 1] *= sizes[i];  // within numel: cannot overflow
+            st[nd - 1] = strides[i];
+        } else {
+            sz[nd] = sizes[i];
+            st[nd] = strides[i];
+            ++nd;
+        }
+    }
+    if (nd == 0) {  // one element
+        sz[0] = 1;
+        st[0] = 1;
+        nd = 1;
+    }
+    return nd;
+}
+
+// Bytes from the source pointer to the end of the last element it reaches:
+// (1 + sum (size_i - 1) * stride_i) * elem_size; false when that overflows.
+static bool gather_extent(int nd, const uint64_t* sz, const uint64_t* st, unsigned elem_size,
+                          uint64_t* extent_bytes) {
+    uint64_t extent = 1;  // elements
+    bool overflow = false;
+    for (int i = 0; i < nd; ++i) {
+        uint64_t span = 0;
+        overflow |= __builtin_mul_overflow(sz[i] - 1, st[i], &span);
+        overflow |= __builtin_add_overflow(extent, span, &extent);
+    }
+    overflow |= __builtin_mul_overflow(extent, (uint64_t)elem_size, extent_bytes);
+    return !overflow;
+}
+
+// The path choice for the collapsed tensor (sz and st may be rewritten; p->src
+// and p->dst_bytes are set already): fills the rest of *p, the element size
+// the kernel runs at (*es_io: 16 on the 16-byte sub-path), the gather kernel's
+// MODE and the number of tiles or patches.  Returns one of CSP_GATHER_PATH_*.
+static int gather_plan(int nd, uint64_t* sz, uint64_t* st, uint64_t numel, bool force_direct,
+                       GatherParams* p, unsigned int* es_io, int* mode, size_t* work) {
+    unsigned int es = *es_io;
+    int path = CSP_GATHER_PATH_DIRECT;
+    const int unit = [&] {  // U: a dimension other than C with source stride 1
+        for (int i = 0; i < nd - 1; ++i)
+            if (st[i] == 1 && sz[i] >= kGatherTransposeMin) return i;
+        return -1;
+    }();
+    if (!force_direct && nd >= 2 && st[nd - 1] != 1 && sz[nd - 1] >= kGatherTransposeMin &&
+        unit >= 0) {
+        *mode = 2;
+        path = CSP_GATHER_PATH_TRANSPOSE;
+        p->numel = numel;
+        uint64_t os[4];  // output strides: row-major
+        os[nd - 1] = 1;
+        for (int i = nd - 2; i >= 0; --i) os[i] = os[i + 1] * sz[i + 1];
+        p->szU = sz[unit];
+        p->osU = os[unit];
+        p->szC = sz[nd - 1];
+        p->ssC = st[nd - 1];
+        p->szR1 = 1;  // R0's size is not needed: it is what is left of the patch index
+        int rest = 0;
+        for (int i = nd - 2; i >= 0; --i) {  // the other dimensions, innermost first
+            if (i == unit) continue;
+            if (rest == 0) { p->szR1 = sz[i]; p->ssR1 = st[i]; p->osR1 = os[i]; }
+            else { p->ssR0 = st[i]; p->osR0 = os[i]; }
+            ++rest;
+        }
+        const uint64_t tu = es <= 4 ? 64 : 32, tc = 64;
+        p->nU = (p->szU + tu - 1) / tu;
+        p->nC = (p->szC + tc - 1) / tc;
+        p->npatch = (numel / (p->szU * p->szC)) * p->nU * p->nC;  // <= numel
+        *work = (size_t)p->npatch;
+    } else {
+        // 16-byte sub-path: the same tensor in 16-byte elements
+        bool wide = es < 16 && st[nd - 1] == 1 && (sz[nd - 1] * es) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(p->src) % 16 == 0;
+        for (int i = 0; wide && i < nd - 1; ++i) wide = (st[i] * es) % 16 == 0;
+        if (wide) {
+            const uint64_t per = 16 / es;
+            sz[nd - 1] /= per;
+            for (int i = 0; i < nd - 1; ++i) st[i] /= per;
+            numel /= per;
+            es = 16;
+            path = CSP_GATHER_PATH_DIRECT16;
+        }
+        *mode = numel < (uint64_t(1) << 32) ? 0 : 1;
+        p->numel = numel;
+        for (int i = 0; i < 4; ++i) {
+            const int j = i - (4 - nd);
+            p->size[i] = j >= 0 ? sz[j] : 1;
+            p->stride[i] = j >= 0 ? st[j] : 0;
+        }
+        for (int i = 0; i < 3; ++i)
+            p->carry[i] = p->stride[i] - p->size[i + 1] * p->stride[i + 1];
+        *work = (size_t)((p->dst_bytes + kPackTileBytes - 1) / kPackTileBytes);
+    }
+    *es_io = es;
+    return path;
+}
+
 // Write the ndim-dimensional strided tensor at device pointer src (sizes and
 // strides in elements of elem_size bytes, as torch gives them) in row-major
 // order to dst and put csp_checksum_dev(dst, dst_bytes) into out[2], from the
@@ -3343,31 +3513,9 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
     out[0] = out[1] = 0;
     if (kernel_ms) *kernel_ms = 0.0;
     if (path_out) *path_out = 0;
-    if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8 &&
-        elem_size != 16) {
-        snprintf(g_err, sizeof(g_err),
-                 "csp_gather_checksum_dev: elem_size %u is not 1, 2, 4, 8 or 16", elem_size);
-        return -1;
-    }
-    if (ndim > 8 || (ndim > 0 && (sizes == nullptr || strides == nullptr))) {
-        snprintf(g_err, sizeof(g_err),
-                 "csp_gather_checksum_dev: %u dimensions (at most 8, with sizes and strides)",
-                 ndim);
-        return -1;
-    }
-    uint64_t numel = 1;
-    bool overflow = false;
-    for (unsigned i = 0; i < ndim; ++i)
-        if (sizes[i] == 0) numel = 0;
-    for (unsigned i = 0; i < ndim && numel != 0; ++i)
-        overflow |= __builtin_mul_overflow(numel, sizes[i], &numel);
-    uint64_t data_bytes = 0;
-    overflow |= __builtin_mul_overflow(numel, (uint64_t)elem_size, &data_bytes);
-    overflow |= data_bytes + 15 < data_bytes;
-    if (overflow) {
-        snprintf(g_err, sizeof(g_err), "csp_gather_checksum_dev: the element count overflows");
-        return -1;
-    }
+    const char* who = "csp_gather_checksum_dev";
+    uint64_t numel = 0, data_bytes = 0;
+    if (!gather_count(who, elem_size, ndim, sizes, strides, &numel, &data_bytes)) return -1;
     if ((uint64_t)dst_bytes != ((data_bytes + 15) & ~uint64_t(15))) {
         snprintf(g_err, sizeof(g_err),
                  "csp_gather_checksum_dev: dst_bytes is %zu, %llu elements of %u bytes need %llu",
@@ -3395,26 +3543,8 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
         return -1;
     }
 
-    // collapse: no size-1 dimensions, contiguous neighbours merged
     uint64_t sz[8], st[8];
-    int nd = 0;
-    for (unsigned i = 0; i < ndim; ++i) {
-        if (sizes[i] == 1) continue;
-        uint64_t run = 0;  // the stride of a neighbour that continues dimension i's rows
-        if (nd > 0 && !__builtin_mul_overflow(strides[i], sizes[i], &run) && st[nd - 1] == run) {
-            sz[nd - 1] *= sizes[i];  // within numel: cannot overflow
-            st[nd - 1] = strides[i];
-        } else {
-            sz[nd] = sizes[i];
-            st[nd] = strides[i];
-            ++nd;
-        }
-    }
-    if (nd == 0) {  // one element
-        sz[0] = 1;
-        st[0] = 1;
-        nd = 1;
-    }
+    const int nd = gather_collapse(ndim, sizes, strides, sz, st);
     if (nd > 4) {
         snprintf(g_err, sizeof(g_err),
                  "csp_gather_checksum_dev: %d dimensions are left after collapsing, at most 4 "
@@ -3422,15 +3552,9 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
         return -1;
     }
     // the source extent, and its overlap with the destination
-    uint64_t extent = 1;  // elements
-    for (int i = 0; i < nd; ++i) {
-        uint64_t span = 0;
-        overflow |= __builtin_mul_overflow(sz[i] - 1, st[i], &span);
-        overflow |= __builtin_add_overflow(extent, span, &extent);
-    }
     uint64_t extent_bytes = 0;
-    overflow |= __builtin_mul_overflow(extent, (uint64_t)elem_size, &extent_bytes);
-    if (overflow || sa + extent_bytes < sa || d + dst_bytes < d) {
+    if (!gather_extent(nd, sz, st, elem_size, &extent_bytes) || sa + extent_bytes < sa ||
+        d + dst_bytes < d) {
         snprintf(g_err, sizeof(g_err), "csp_gather_checksum_dev: an address range overflows");
         return -1;
     }
@@ -3446,61 +3570,10 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
     p.dst = static_cast<unsigned char*>(dst);
     p.dst_bytes = dst_bytes;
     unsigned int es = elem_size;
-    int mode = 0, path = CSP_GATHER_PATH_DIRECT;
+    int mode = 0;
     size_t work = 0;  // tiles or patches
-    const int unit = [&] {  // U: a dimension other than C with source stride 1
-        for (int i = 0; i < nd - 1; ++i)
-            if (st[i] == 1 && sz[i] >= kGatherTransposeMin) return i;
-        return -1;
-    }();
-    if (g_gather_force_path != 1 && nd >= 2 && st[nd - 1] != 1 &&
-        sz[nd - 1] >= kGatherTransposeMin && unit >= 0) {
-        mode = 2;
-        path = CSP_GATHER_PATH_TRANSPOSE;
-        p.numel = numel;
-        uint64_t os[4];  // output strides: row-major
-        os[nd - 1] = 1;
-        for (int i = nd - 2; i >= 0; --i) os[i] = os[i + 1] * sz[i + 1];
-        p.szU = sz[unit];
-        p.osU = os[unit];
-        p.szC = sz[nd - 1];
-        p.ssC = st[nd - 1];
-        p.szR1 = 1;  // R0's size is not needed: it is what is left of the patch index
-        int rest = 0;
-        for (int i = nd - 2; i >= 0; --i) {  // the other dimensions, innermost first
-            if (i == unit) continue;
-            if (rest == 0) { p.szR1 = sz[i]; p.ssR1 = st[i]; p.osR1 = os[i]; }
-            else { p.ssR0 = st[i]; p.osR0 = os[i]; }
-            ++rest;
-        }
-        const uint64_t tu = es <= 4 ? 64 : 32, tc = 64;
-        p.nU = (p.szU + tu - 1) / tu;
-        p.nC = (p.szC + tc - 1) / tc;
-        p.npatch = (numel / (p.szU * p.szC)) * p.nU * p.nC;  // <= numel
-        work = (size_t)p.npatch;
-    } else {
-        // 16-byte sub-path: the same tensor in 16-byte elements
-        bool wide = es < 16 && st[nd - 1] == 1 && (sz[nd - 1] * es) % 16 == 0 && sa % 16 == 0;
-        for (int i = 0; wide && i < nd - 1; ++i) wide = (st[i] * es) % 16 == 0;
-        if (wide) {
-            const uint64_t per = 16 / es;
-            sz[nd - 1] /= per;
-            for (int i = 0; i < nd - 1; ++i) st[i] /= per;
-            numel /= per;
-            es = 16;
-            path = CSP_GATHER_PATH_DIRECT16;
-        }
-        mode = numel < (uint64_t(1) << 32) ? 0 : 1;
-        p.numel = numel;
-        for (int i = 0; i < 4; ++i) {
-            const int j = i - (4 - nd);
-            p.size[i] = j >= 0 ? sz[j] : 1;
-            p.stride[i] = j >= 0 ? st[j] : 0;
-        }
-        for (int i = 0; i < 3; ++i)
-            p.carry[i] = p.stride[i] - p.size[i + 1] * p.stride[i + 1];
-        work = (dst_bytes + kPackTileBytes - 1) / kPackTileBytes;
-    }
+    const int path = gather_plan(nd, sz, st, numel, g_gather_force_path == 1, &p, &es, &mode,
+                                 &work);
 
     // one accumulator pair per process, one call at a time
     std::lock_guard<std::mutex> lock(g_checksum_mu);
@@ -3553,6 +3626,425 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
     out[0] = host[0];
     out[1] = host[1];
     if (path_out) *path_out = path;
+    return done(0);
+}
+
+// ---------------------------------------------------------------------------
+// Packed gather with checksum: contiguous and strided sources, one arena
+// ---------------------------------------------------------------------------
+//
+// The packed result arena (csp_pack_dev's layout rule) filled by ONE launch
+// from a mix of contiguous and non-contiguous tensors, with
+// csp_checksum_dev(arena, arena_bytes) from the same pass.  A channels_last
+// state dict, .t() views of Linear weights or per-head slices of a fused
+// weight no longer cost one contiguous() (a launch, an allocation, a read and
+// a write) per tensor before the pack kernel starts.
+//
+// The host turns every non-empty segment into one table entry of one of three
+// kinds and counts its work units; `unit_begin` is the strictly increasing
+// prefix of those counts.  A workgroup takes unit = blockIdx.x, += gridDim.x,
+// finds the entry by the pack kernel's binary search (the unit index alone
+// decides, so kind and element size are wave-uniform and the entry is read
+// with scalar loads), and runs one body behind a uniform branch:
+//
+//   - COPY: contiguous bytes at any alignment, a 16 KiB tile per unit:
+//     pack_checksum_tile<ALIGN>, as in csp_pack_checksum_kernel;
+//   - DIRECT: a strided source, a 16 KiB tile of the segment's output per
+//     unit: gather_direct with 32-bit element indices (the host refuses
+//     2^32 elements), the 16-byte sub-path included;
+//   - TRANSPOSE: a strided source, one patch per unit through the LDS tile:
+//     gather_transpose_patch, the body of csp_gather_checksum_kernel.
+//
+// LDS: one tile of 33 792 bytes, what the 16-byte transpose needs, used by
+// TRANSPOSE units of every element size; with the 64 bytes of the final
+// reduction four workgroups per CU take 132.3 KiB of the 160 KiB.  COPY and
+// DIRECT units do not touch LDS at all, and a patch ends with the barrier that
+// frees the tile, so a unit of any kind may follow a patch in a workgroup.
+// The barriers sit inside the uniform branch: every lane of the workgroup
+// takes it.
+//
+// The per-lane u64 s0/t accumulators are carried across all units whatever
+// their kinds; word indices are arena-global (dst_off / 4 + 4 * vi for whole
+// vectors, dst_off + b for the elements of patch edges), and the arena stays
+// at or below 16 GiB, so none reaches 2^32.  Every arena byte is written
+// exactly once, nothing outside the arena is written, sources and the table
+// are only read.  No MFMA: nothing is multiplied.
+//
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): no scratch, no
+// spills; the figures are in profiles/packed_strided_results.md.
+#define CSP_PACK_GATHER_COPY 0
+#define CSP_PACK_GATHER_DIRECT 1
+#define CSP_PACK_GATHER_TRANSPOSE 2
+
+#define CSP_GATHER_PATH_COPY 4  // path_out of a contiguous segment
+
+struct PackGatherEntry {
+    // COPY: src alone.  The strided kinds: all of it, with dst == arena +
+    // dst_off and dst_bytes == round_up(nbytes, 16)
+    GatherParams g;
+    unsigned long long dst_off;
+    unsigned long long nbytes;      // data bytes
+    unsigned long long unit_begin;  // units owned by the entries before this one
+    unsigned int kind;              // CSP_PACK_GATHER_*
+    unsigned int es;                // the element size the body runs at
+};
+
+static const int kPackGatherTileBytes = GatherTile<16>::TC * GatherTile<16>::PITCH;
+static_assert(kPackGatherTileBytes >= GatherTile<8>::TC * GatherTile<8>::PITCH &&
+              kPackGatherTileBytes >= GatherTile<4>::TC * GatherTile<4>::PITCH &&
+              kPackGatherTileBytes >= GatherTile<2>::TC * GatherTile<2>::PITCH &&
+              kPackGatherTileBytes >= GatherTile<1>::TC * GatherTile<1>::PITCH,
+              "the tile serves every element size");
+static_assert(4 * (kPackGatherTileBytes + 64) <= 160 * 1024, "four workgroups per CU");
+
+__global__ __launch_bounds__(256) void csp_pack_gather_checksum_kernel(
+    const PackGatherEntry* __restrict__ segs, unsigned int nseg, unsigned long long total_units,
+    unsigned char* __restrict__ arena, unsigned long long* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) unsigned char tile[kPackGatherTileBytes];
+    unsigned long long s0 = 0, t = 0;
+    for (unsigned long long unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
+        // last entry whose first unit is <= unit (unit_begin is strictly
+        // increasing: the host leaves zero-byte segments out of the table)
+        unsigned int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].unit_begin <= unit) lo = mid; else hi = mid;
+        }
+        const PackGatherEntry& e = segs[lo];
+        const unsigned long long u = unit - e.unit_begin;
+        const unsigned long long dst_off = e.dst_off;
+        // arena-global index of the segment's first word
+        const unsigned int word_base = (unsigned int)(dst_off / 4);
+        const unsigned int kind = e.kind;
+        if (kind == CSP_PACK_GATHER_COPY) {
+            const pack_src_t src = (pack_src_t)e.g.src;
+            u32x4* dst = reinterpret_cast<u32x4*>(arena + dst_off);
+            const unsigned long long n = e.nbytes;
+            const unsigned int a = (unsigned int)(reinterpret_cast<uintptr_t>(e.g.src) & 15u);
+            if (a == 0) pack_checksum_tile<16>(src, dst, n, u, word_base, s0, t);
+            else if ((a & 7u) == 0) pack_checksum_tile<8>(src, dst, n, u, word_base, s0, t);
+            else if ((a & 3u) == 0) pack_checksum_tile<4>(src, dst, n, u, word_base, s0, t);
+            else if ((a & 1u) == 0) pack_checksum_tile<2>(src, dst, n, u, word_base, s0, t);
+            else pack_checksum_tile<1>(src, dst, n, u, word_base, s0, t);
+            continue;
+        }
+        const GatherParams& p = e.g;  // its fields are loaded where a body uses them
+        const unsigned int es = e.es;
+        if (kind == CSP_PACK_GATHER_DIRECT) {
+            if (es == 16) gather_direct<16, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
+            else if (es == 8) gather_direct<8, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
+            else if (es == 4) gather_direct<4, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
+            else if (es == 2) gather_direct<2, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
+            else gather_direct<1, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
+        } else {
+            if (es == 16) gather_transpose_patch<16>(p, tile, u, dst_off, s0, t);
+            else if (es == 8) gather_transpose_patch<8>(p, tile, u, dst_off, s0, t);
+            else if (es == 4) gather_transpose_patch<4>(p, tile, u, dst_off, s0, t);
+            else if (es == 2) gather_transpose_patch<2>(p, tile, u, dst_off, s0, t);
+            else gather_transpose_patch<1>(p, tile, u, dst_off, s0, t);
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+// At most 1024 blocks, the cap of the other kernels that carry a checksum.
+// Carried over, not measured for this kernel.
+static const size_t kPackGatherGridCapDefault = 1024;
+static size_t g_pack_gather_grid_cap = kPackGatherGridCapDefault;
+static int g_pack_gather_force_path = 0;
+
+// Tools only: the grid cap of the next csp_pack_gather_checksum_dev calls
+// (0 restores the default).  Returns the cap in effect.  With a cap of 1, 2
+// or 3 blocks every block walks units of every kind in turn.
+extern "C" size_t csp_pack_gather_checksum_grid_cap(size_t cap) {
+    g_pack_gather_grid_cap = cap ? std::min(cap, size_t(65536)) : kPackGatherGridCapDefault;
+    return g_pack_gather_grid_cap;
+}
+
+// Tools only: 1 makes the next csp_pack_gather_checksum_dev calls take DIRECT
+// where the host would choose TRANSPOSE, 0 restores the host's choice.
+// Returns the value in effect.
+extern "C" int csp_pack_gather_checksum_path(int force) {
+    g_pack_gather_force_path = force == 1 ? 1 : 0;
+    return g_pack_gather_force_path;
+}
+
+// Whether the packed gather serves this strided layout, and what it needs to
+// know of it: element size 1, 2, 4, 8 or 16, at most 8 dimensions, at most 4
+// after collapsing, fewer than 2^32 elements, no overflow.  false with a
+// message that `who` opens.  No device code.
+static bool gather_served(const char* who, unsigned elem_size, unsigned ndim,
+                          const uint64_t* shape, const uint64_t* stride, uint64_t* numel,
+                          uint64_t* data_bytes, uint64_t sz[8], uint64_t st[8], int* nd,
+                          uint64_t* extent_bytes) {
+    if (!gather_count(who, elem_size, ndim, shape, stride, numel, data_bytes)) return false;
+    if (*numel >= (uint64_t(1) << 32)) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: %llu elements, a strided segment holds fewer than 2^32", who,
+                 (unsigned long long)*numel);
+        return false;
+    }
+    *nd = 0;
+    *extent_bytes = 0;
+    if (*numel == 0) return true;
+    *nd = gather_collapse(ndim, shape, stride, sz, st);
+    if (*nd > 4) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: %d dimensions are left after collapsing, at most 4 are served", who, *nd);
+        return false;
+    }
+    if (!gather_extent(*nd, sz, st, elem_size, extent_bytes)) {
+        snprintf(g_err, sizeof(g_err), "%s: the source extent overflows", who);
+        return false;
+    }
+    return true;
+}
+
+// 1 when csp_pack_gather_checksum_dev serves a strided segment of this layout
+// (shape and stride in elements, as torch reports them), else 0 with the
+// reason in csp_last_error().  Host only: nothing is launched.
+extern "C" int csp_gather_supported(unsigned elem_size, unsigned ndim, const uint64_t* shape,
+                                    const uint64_t* stride) {
+    uint64_t numel = 0, data_bytes = 0, extent_bytes = 0, sz[8], st[8];
+    int nd = 0;
+    return gather_served("csp_gather_supported", elem_size, ndim, shape, stride, &numel,
+                         &data_bytes, sz, st, &nd, &extent_bytes) ? 1 : 0;
+}
+
+// One segment of csp_pack_gather_checksum_dev.  Plain C, fixed layout, 160
+// bytes: ndim == 0 is nbytes contiguous bytes at src (any alignment); ndim
+// 1..8 is a strided tensor of elem_size-byte elements at src (aligned to
+// elem_size) with shape and stride in elements, as torch reports them, and
+// nbytes == numel * elem_size.  Entries of shape and stride past ndim are
+// ignored.
+struct CspPackGatherSeg {
+    const void* src;
+    uint64_t dst_off, nbytes;
+    uint32_t elem_size, ndim;
+    uint64_t shape[8], stride[8];
+};
+static_assert(sizeof(CspPackGatherSeg) == 160, "the layout the bindings declare");
+
+// Fill `arena` from nseg segments under csp_pack_dev's layout rule (segment k
+// at dst_off[k], each at the next multiple of 16 after the one before, the
+// padding zero) and put csp_checksum_dev(arena, arena_bytes) into out[2], from
+// ONE launch.  A strided segment lands in row-major order.  Stride 0 is
+// valid; a zero-byte segment owns no unit.  Returns -1 with a message that
+// names the segment and launches nothing for: everything
+// csp_pack_checksum_dev refuses (the layout rule and the total, a misaligned
+// or null arena, a null source with bytes, overflow, an arena above 16 GiB,
+// 2^31 segments or more); a strided segment that csp_gather_supported does
+// not serve or whose source is not aligned to elem_size; nbytes that is not
+// numel * elem_size; and a source extent (nbytes for a contiguous segment,
+// (1 + sum (size_i - 1) * stride_i) * elem_size for a strided one) that
+// overlaps the arena (ranges that only touch are fine, sources may overlap
+// each other).  path_out (optional, nseg entries): what each segment took,
+// CSP_GATHER_PATH_* (4: COPY), 0 for a zero-byte one; all 0 on failure.  A
+// strided segment that collapses to one contiguous run is a COPY.  Runs on
+// copy_stream() and synchronises it before returning; sources written on
+// another stream must be complete first.  kernel_ms (optional): the kernel
+// alone, from events around the launch.
+extern "C" int csp_pack_gather_checksum_dev(const CspPackGatherSeg* segs, size_t nseg,
+                                            void* arena, size_t arena_bytes, uint64_t out[2],
+                                            double* kernel_ms, int* path_out) {
+    const char* fn = "csp_pack_gather_checksum_dev";
+    out[0] = out[1] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (nseg >= (size_t(1) << 31)) {  // before anything walks the segments
+        snprintf(g_err, sizeof(g_err), "%s: %zu segments are too many", fn, nseg);
+        return -1;
+    }
+    if (path_out) std::fill(path_out, path_out + nseg, 0);
+    if ((uint64_t)arena_bytes > kPackChecksumMaxBytes) {
+        snprintf(g_err, sizeof(g_err), "%s: arena_bytes %zu is above 16 GiB", fn, arena_bytes);
+        return -1;
+    }
+    const uintptr_t a = reinterpret_cast<uintptr_t>(arena);
+    if (a + arena_bytes < a) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at arena %p overflow", fn, arena_bytes,
+                 arena);
+        return -1;
+    }
+    if (a % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: arena pointer %p is not 16-byte aligned", fn, arena);
+        return -1;
+    }
+    std::vector<PackGatherEntry> table;
+    std::vector<int> paths(nseg, 0);
+    table.reserve(nseg);
+    uint64_t expect = 0, units = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        const CspPackGatherSeg& g = segs[k];
+        char who[64];
+        snprintf(who, sizeof(who), "%s: segment %zu", fn, k);
+        if (g.dst_off != expect) {
+            snprintf(g_err, sizeof(g_err), "%s: dst_off is %llu, the layout rule gives %llu", who,
+                     (unsigned long long)g.dst_off, (unsigned long long)expect);
+            return -1;
+        }
+        const uint64_t rounded = (g.nbytes + 15) & ~uint64_t(15);
+        if (rounded < g.nbytes || expect + rounded < expect) {
+            snprintf(g_err, sizeof(g_err), "%s overflows", who);
+            return -1;
+        }
+        uint64_t numel = 0, data_bytes = 0, extent_bytes = g.nbytes, sz[8], st[8];
+        int nd = 0;
+        if (g.ndim > 0) {
+            if (!gather_served(who, g.elem_size, g.ndim, g.shape, g.stride, &numel, &data_bytes,
+                               sz, st, &nd, &extent_bytes))
+                return -1;
+            if (data_bytes != g.nbytes) {
+                snprintf(g_err, sizeof(g_err),
+                         "%s: nbytes is %llu, %llu elements of %u bytes are %llu", who,
+                         (unsigned long long)g.nbytes, (unsigned long long)numel, g.elem_size,
+                         (unsigned long long)data_bytes);
+                return -1;
+            }
+        }
+        expect += rounded;
+        if (g.nbytes == 0) continue;  // owns no unit
+        const uintptr_t sa = reinterpret_cast<uintptr_t>(g.src);
+        if (sa == 0) {
+            snprintf(g_err, sizeof(g_err), "%s has %llu bytes at a null pointer", who,
+                     (unsigned long long)g.nbytes);
+            return -1;
+        }
+        if (g.ndim > 0 && sa % g.elem_size != 0) {
+            snprintf(g_err, sizeof(g_err), "%s: src %p is not aligned to %u bytes", who, g.src,
+                     g.elem_size);
+            return -1;
+        }
+        if (sa + extent_bytes < sa) {
+            snprintf(g_err, sizeof(g_err), "%s: src %p with %llu bytes overflows", who, g.src,
+                     (unsigned long long)extent_bytes);
+            return -1;
+        }
+        if (sa < a + arena_bytes && a < sa + extent_bytes) {
+            snprintf(g_err, sizeof(g_err), "%s: %llu source bytes at %p overlap the arena at %p",
+                     who, (unsigned long long)extent_bytes, g.src, arena);
+            return -1;
+        }
+        PackGatherEntry e = {};
+        e.g.src = static_cast<const unsigned char*>(g.src);
+        e.g.dst = static_cast<unsigned char*>(arena) + g.dst_off;
+        e.g.dst_bytes = rounded;
+        e.dst_off = g.dst_off;
+        e.nbytes = g.nbytes;
+        e.unit_begin = units;
+        if (g.ndim == 0 || (nd == 1 && st[0] == 1)) {  // one contiguous run
+            e.kind = CSP_PACK_GATHER_COPY;
+            e.es = 1;
+            paths[k] = CSP_GATHER_PATH_COPY;
+            units += (rounded + kPackTileBytes - 1) / kPackTileBytes;
+        } else {
+            int mode = 0;
+            size_t work = 0;
+            e.es = g.elem_size;
+            paths[k] = gather_plan(nd, sz, st, numel, g_pack_gather_force_path == 1, &e.g, &e.es,
+                                   &mode, &work);
+            e.kind = mode == 2 ? CSP_PACK_GATHER_TRANSPOSE : CSP_PACK_GATHER_DIRECT;
+            units += work;
+        }
+        table.push_back(e);
+    }
+    if (expect != (uint64_t)arena_bytes) {
+        snprintf(g_err, sizeof(g_err), "%s: arena_bytes is %zu, the segments need %llu", fn,
+                 arena_bytes, (unsigned long long)expect);
+        return -1;
+    }
+    if (table.empty()) return 0;
+    if (arena == nullptr) {
+        snprintf(g_err, sizeof(g_err), "%s: null arena for %zu bytes", fn, arena_bytes);
+        return -1;
+    }
+
+    // one accumulator pair and one grow-only table per process, one call at
+    // a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static PackGatherEntry* dev_table = nullptr;
+    static size_t dev_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_device != device) {
+        if (acc) (void)hipFree(acc);
+        if (dev_table) (void)hipFree(dev_table);
+        acc = nullptr;
+        dev_table = nullptr;
+        dev_cap = 0;
+        dev_device = device;
+    }
+    if (acc == nullptr) HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+    if (dev_table == nullptr || dev_cap < table.size()) {
+        if (dev_table) (void)hipFree(dev_table);
+        dev_table = nullptr;
+        dev_cap = 0;
+        size_t cap = 256;
+        while (cap < table.size()) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_table, cap * sizeof(PackGatherEntry)));
+        dev_cap = cap;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define PACKGATHER_TRY(expr)                                       \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    // `table` outlives the copy: the stream is synchronised below
+    PACKGATHER_TRY(hipMemcpyAsync(dev_table, table.data(),
+                                  table.size() * sizeof(PackGatherEntry),
+                                  hipMemcpyHostToDevice, s));
+    PACKGATHER_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t blocks = (size_t)std::min<uint64_t>(units, g_pack_gather_grid_cap);
+    if (t0) PACKGATHER_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_pack_gather_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0,
+                       s, dev_table, (unsigned int)table.size(), (unsigned long long)units,
+                       static_cast<unsigned char*>(arena), acc);
+    PACKGATHER_TRY(hipGetLastError());
+    if (t1) PACKGATHER_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    PACKGATHER_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    PACKGATHER_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        PACKGATHER_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef PACKGATHER_TRY
+    out[0] = host[0];
+    out[1] = host[1];
+    if (path_out) std::copy(paths.begin(), paths.end(), path_out);
     return done(0);
 }
 

@@ -116,8 +116,14 @@ Protocol (all frames: 8-byte big-endian length + payload):
              contiguous(); the frames and their meta are the same bytes
              either way, meta["staging"] counts "gathered_tensors" and
              "gathered_bytes", and a tensor the kernel refuses takes
-             contiguous() with the reason in "gather_fallback".  A zero-length
-             request frame means: shut down.
+             contiguous() with the reason in "gather_fallback".  The packed
+             arena likewise: its non-contiguous tensors that
+             csp_gather_supported serves stay as they are and ONE
+             csp_pack_gather_checksum_dev call fills and sums the arena from
+             contiguous and strided tensors together; the others (more than 4
+             dimensions after collapsing, conjugated or negated views) take
+             contiguous() one by one, and a refusal of the call sends all of
+             them that way.  A zero-length request frame means: shut down.
 
 The worker's REAL stdout is reserved for the protocol; fd 1 is
 re-pointed at stderr before any user code runs, so user prints cannot
@@ -350,6 +356,24 @@ def _load_gpu_lib():
             ctypes.POINTER(ctypes.c_double),
             ctypes.POINTER(ctypes.c_int),
         ]
+    if GATHER_RESULTS and hasattr(lib, "csp_pack_gather_checksum_dev"):
+        lib.csp_pack_gather_checksum_dev.restype = ctypes.c_int
+        lib.csp_pack_gather_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_double),
+            ctypes.POINTER(ctypes.c_int),
+        ]
+        lib.csp_gather_supported.restype = ctypes.c_int
+        lib.csp_gather_supported.argtypes = [
+            ctypes.c_uint,
+            ctypes.c_uint,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint64),
+        ]
     lib.csp_patch_unpack_checksum_dev.restype = ctypes.c_int
     lib.csp_patch_unpack_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -531,6 +555,63 @@ def _gather_into(lib, t, dst_ptr, total, stats):
     return [int(out[0]), int(out[1])]
 
 
+def _packs_strided(lib, t):
+    """Whether the non-contiguous CUDA tensor ``t`` stays as it is in the
+    packed arena, as a strided segment of csp_pack_gather_checksum_dev."""
+    import ctypes
+
+    if not (_gathers(lib, t) and hasattr(lib, "csp_pack_gather_checksum_dev")):
+        return False
+    dims = t.dim()
+    if not 0 < dims <= 8 or min(t.stride()) < 0:
+        return False
+    return bool(lib.csp_gather_supported(
+        t.element_size(), dims,
+        (ctypes.c_uint64 * dims)(*t.shape), (ctypes.c_uint64 * dims)(*t.stride()),
+    ))
+
+
+def _pack_gather_checksum(lib, segments, arena_ptr, total):
+    """One csp_pack_gather_checksum_dev call on ``segments``, (tensor, offset,
+    nbytes, strided) each; returns [s0, s1] of the arena."""
+    import ctypes
+
+    count = len(segments)
+    # CspPackGatherSeg as 20 u64: src, dst_off, nbytes, elem_size | ndim << 32,
+    # shape[8], stride[8]
+    table = (ctypes.c_uint64 * (20 * count))()
+    for k, (t, off, n, strided) in enumerate(segments):
+        row = [t.data_ptr() if n else 0, off, n, 0] + [0] * 16
+        if strided:
+            dims = t.dim()
+            row[3] = t.element_size() | dims << 32
+            row[4 : 4 + dims] = t.shape
+            row[12 : 12 + dims] = t.stride()
+        table[20 * k : 20 * k + 20] = row
+    out = (ctypes.c_uint64 * 2)()
+    rc = lib.csp_pack_gather_checksum_dev(
+        table, count, ctypes.c_void_p(arena_ptr), total, out, None, None
+    )
+    if rc != 0:
+        raise RuntimeError(
+            "csp_pack_gather_checksum_dev failed (rc=%d): %s"
+            % (rc, lib.csp_last_error().decode(errors="replace"))
+        )
+    return [int(out[0]), int(out[1])]
+
+
+def _flat_sources(segments):
+    """The sources of ``segments`` as without gather_tensor_results:
+    contiguous() for all.  Returns (the tensors, their pointers)."""
+    import torch
+
+    flats = [t.contiguous() for t, _, _, _ in segments]
+    torch.cuda.synchronize()  # the library's copy stream does not wait on the null stream
+    return flats, [
+        (f.data_ptr() or None) if n else None for f, (_, _, n, _) in zip(flats, segments)
+    ]
+
+
 def _retain_buffer(lib, retain, index, src_ptrs, offsets, sizes, total, nbytes, stats,
                    keep=True, gather=None):
     """Result buffer ``index`` gathered, copied and checksummed by one
@@ -544,7 +625,13 @@ def _retain_buffer(lib, retain, index, src_ptrs, offsets, sizes, total, nbytes, 
 
     ``gather`` (gather_tensor_results): the one strided tensor that makes up
     the buffer; ONE csp_gather_checksum_dev call fills the buffer from it, and
-    only when that is refused does torch lay it out for the pack kernel."""
+    only when that is refused does torch lay it out for the pack kernel.
+
+    ``src_ptrs`` may instead be the segment list of _pack_gather_checksum (a
+    packed arena with strided tensors in it, ``offsets`` and ``sizes`` then
+    None): ONE csp_pack_gather_checksum_dev call fills the buffer; when that
+    is refused, stats["gather_fallback"] says why and torch lays every tensor
+    out for the pack kernel."""
     global _arg_cache_resident
     import torch
 
@@ -573,6 +660,15 @@ def _retain_buffer(lib, retain, index, src_ptrs, offsets, sizes, total, nbytes, 
                 flat = gather.contiguous()
                 torch.cuda.synchronize()
                 src_ptrs = [flat.data_ptr()]
+        if offsets is None:
+            segments = src_ptrs
+            try:
+                sums = _pack_gather_checksum(lib, segments, arena.data_ptr(), total)
+            except Exception as e:  # noqa: BLE001 - a gather never fails a task
+                stats["gather_fallback"] = repr(e)[:500]
+                flats, src_ptrs = _flat_sources(segments)
+                offsets = [off for _, off, _, _ in segments]
+                sizes = [n for _, _, n, _ in segments]
         if sums is None:
             sums = _pack_checksum(lib, src_ptrs, offsets, sizes, arena.data_ptr(), total)
     except Exception as e:  # noqa: BLE001 - retention never fails a task
@@ -658,7 +754,13 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
     _retain_large_bytes(), one csp_pack_checksum_dev call stands in for
     csp_pack_dev and csp_checksum_dev, and an arena of at least
     max(1, RETAIN_MIN_BYTES) bytes stays in HBM as an argument master
-    (_retain_buffer); when that fails the two calls run as without it."""
+    (_retain_buffer); when that fails the two calls run as without it.
+
+    With GATHER_RESULTS a non-contiguous tensor that _packs_strided accepts
+    stays as it is, and when there is one, ONE csp_pack_gather_checksum_dev
+    call fills and sums the arena, retained or not; its refusal goes to
+    stats["gather_fallback"] and the calls above run with contiguous() for
+    all."""
     import ctypes
 
     import torch
@@ -671,8 +773,10 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
         return {}
     name = None
     try:
-        # torch makes non-contiguous tensors contiguous, as on the large path
-        srcs = [t.contiguous() for t in tensors]
+        # torch makes non-contiguous tensors contiguous, as on the large path,
+        # but for those that go into the arena as strided segments
+        strided = [n > 0 and _packs_strided(lib, t) for t, n in zip(tensors, sizes)]
+        srcs = [t if s else t.contiguous() for t, s in zip(tensors, strided)]
         offsets = []
         total = 0
         for n in sizes:
@@ -682,16 +786,26 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
         torch.cuda.synchronize()
         count = len(srcs)
         ptrs = [(t.data_ptr() or None) if n else None for t, n in zip(srcs, sizes)]
+        segments = list(zip(srcs, offsets, sizes, strided)) if any(strided) else None
         kept = None
         if retain is not None:
             kept = _retain_buffer(
-                lib, retain, len(buffers), ptrs, offsets, sizes, total, total, stats,
-                keep=total >= max(1, RETAIN_MIN_BYTES),
+                lib, retain, len(buffers), segments or ptrs, None if segments else offsets,
+                sizes, total, total, stats, keep=total >= max(1, RETAIN_MIN_BYTES),
             )
         if kept is not None:
             arena, sums, name = kept
         else:
             arena = torch.empty(total, dtype=torch.uint8, device="cuda")
+            sums = None
+            if segments is not None and "gather_fallback" not in stats:
+                try:  # this one call stands in for csp_pack_dev and csp_checksum_dev
+                    sums = _pack_gather_checksum(lib, segments, arena.data_ptr(), total)
+                except Exception as e:  # noqa: BLE001 - a gather never fails a task
+                    stats["gather_fallback"] = repr(e)[:500]
+            if sums is None and segments is not None:
+                srcs, ptrs = _flat_sources(segments)
+        if kept is None and sums is None:
             rc = lib.csp_pack_dev(
                 (ctypes.c_void_p * count)(*ptrs), (ctypes.c_uint64 * count)(*offsets),
                 (ctypes.c_uint64 * count)(*sizes), count,
@@ -709,6 +823,11 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
                     "csp_checksum_dev failed (rc=%d): %s"
                     % (rc, lib.csp_last_error().decode(errors="replace"))
                 )
+        if segments is not None and "gather_fallback" not in stats:
+            stats["gathered_tensors"] = stats.get("gathered_tensors", 0) + sum(strided)
+            stats["gathered_bytes"] = stats.get("gathered_bytes", 0) + sum(
+                n for n, s in zip(sizes, strided) if s
+            )
     except Exception as e:  # noqa: BLE001 - packing never fails a task
         stats["pack_fallback"] = repr(e)[:500]
         return {}

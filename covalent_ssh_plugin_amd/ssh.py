@@ -194,7 +194,12 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # library's own gather kernel in ONE pass, straight into the retained
     # master (with its checksum) or into the buffer its frame is streamed
     # from, where torch's contiguous() costs a second full-size allocation and
-    # a second read and write.  The wire format does not change.
+    # a second read and write.  With pack_tensor_results the packed arena is
+    # covered too: its non-contiguous tensors (a channels_last state dict,
+    # .t() views, slices) stay as they are and one launch fills and sums the
+    # arena from contiguous and strided tensors together, where contiguous()
+    # costs a launch and an allocation per tensor.  The wire format does not
+    # change.
     "gather_tensor_results": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
