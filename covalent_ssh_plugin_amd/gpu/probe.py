@@ -725,7 +725,7 @@ def diff_checksum_grid_cap(cap: int = 0) -> int:
     return int(load().csp_diff_checksum_grid_cap(int(cap)))
 
 
-GATHER_PATHS = {0: "none", 1: "direct", 2: "direct16", 3: "transpose"}
+GATHER_PATHS = {0: "none", 1: "direct", 2: "direct16", 3: "transpose", 5: "slab"}
 
 
 def gather_checksum_device(
@@ -739,7 +739,10 @@ def gather_checksum_device(
     the padding is stored as zero.  Returns ``{"sums": (s0, s1), "kernel_ms",
     "path"}``: ``sums`` equals ``checksum_device(dst_ptr, dst_bytes)``,
     ``path`` is ``"direct"`` (per-element loads), ``"direct16"`` (16-byte
-    loads), ``"transpose"`` (through an LDS tile) or ``"none"`` (no element).
+    loads), ``"transpose"`` (through an LDS tile), ``"slab"`` (a short inner
+    dimension under the unit-stride one, such as a ``channels_last`` 3 x 3
+    weight, through an LDS slab in output order; only under
+    ``gather_checksum_path(2)``) or ``"none"`` (no element).
     An element size outside 1, 2, 4, 8, 16, more than 4 dimensions after
     collapsing, a null or misaligned pointer, a wrong ``dst_bytes`` or a source
     extent that overlaps the destination raises ``GpuLibError`` and launches
@@ -776,7 +779,9 @@ def gather_checksum_grid_cap(cap: int = 0) -> int:
 
 def gather_checksum_path(force: int = 0) -> int:
     """Tools only: 1 forces the direct path of :func:`gather_checksum_device`,
-    0 restores the host's choice.  Returns the value in effect."""
+    2 takes the slab path wherever its rule holds (the host does not choose it
+    by itself: it measured slower than the direct path), 0 restores the host's
+    choice.  Returns the value in effect."""
     return int(load().csp_gather_checksum_path(int(force)))
 
 
@@ -811,7 +816,8 @@ def pack_gather_checksum_device(segments, arena_ptr: int, arena_bytes: int) -> d
     order; offsets follow :func:`pack_layout`.  Returns ``{"sums": (s0, s1),
     "kernel_ms", "paths"}``: ``sums`` equals ``checksum_device(arena_ptr,
     arena_bytes)``, ``paths`` has one of ``"copy"``, ``"direct"``,
-    ``"direct16"``, ``"transpose"`` or ``"none"`` (no byte) per segment.
+    ``"direct16"``, ``"transpose"``, ``"slab"`` or ``"none"`` (no byte) per
+    segment.
     Refuses what :func:`pack_checksum_device` refuses, a strided segment that
     :func:`gather_supported` does not serve, an ``nbytes`` that disagrees with
     the shape, and a source extent that overlaps the arena (``GpuLibError``
@@ -859,8 +865,9 @@ def pack_gather_checksum_grid_cap(cap: int = 0) -> int:
 
 def pack_gather_checksum_path(force: int = 0) -> int:
     """Tools only: 1 makes :func:`pack_gather_checksum_device` take the direct
-    path where the host would choose the transpose, 0 restores the host's
-    choice.  Returns the value in effect."""
+    path where the host would choose the transpose, 2 makes it take the slab
+    path wherever its rule holds (the host does not choose it by itself), 0
+    restores the host's choice.  Returns the value in effect."""
     return int(load().csp_pack_gather_checksum_path(int(force)))
 
 

@@ -3010,7 +3010,7 @@ extern "C" int csp_diff_checksum_dev(const void* cur, const void* base, size_t n
 //
 // The host drops size-1 dimensions and merges neighbours that are contiguous
 // with each other, refuses what is left above 4 dimensions, and picks one of
-// two paths per call, so the choice is uniform for every wave:
+// three paths per call, so the choice is uniform for every wave:
 //
 //   - DIRECT: the pack kernel's decomposition of the OUTPUT: 16 KiB tiles,
 //     256 threads, four 16-byte vectors per lane, blocks looping
@@ -3047,16 +3047,68 @@ extern "C" int csp_diff_checksum_dev(const void* cur, const void* base, size_t n
 //     of the output adds value << 8 * (b % 4) to s0 and the same times the
 //     word weight to t.  Every output byte is written exactly once, by one
 //     lane; the lane that stores the last element also stores the zero
-//     padding behind it.
+//     padding behind it;
+//   - SLAB: NOT the host's choice today, because it measured slower than
+//     DIRECT (below); a tools-only force value reaches it, so that tests and
+//     measurements can.  It serves a short C, 2 to kGatherTransposeMin - 1
+//     elements with a source stride other than 1, whose neighbour directly
+//     above is U: source stride 1 and at least kGatherTransposeMin elements.  That
+//     is a channels_last 3 x 3 weight (O, I, 3, 3), which collapses to
+//     (O, I, 9) with strides (9 I, 1, I), and as well 5 x 5, 2 x 2 and 4 x 4
+//     kernels and any permute that leaves such a pair innermost.  For fixed
+//     outer coordinates a run of TU values of U times all of C is ONE
+//     contiguous piece of the output, TU * szC elements, made of szC source
+//     rows of TU unit-stride elements: a slab.  TU = 256 / ES, so a source
+//     row is 256 bytes whatever the element size, and a full slab is
+//     256 * szC bytes, a multiple of 16.  A workgroup owns a slab and loops
+//     slab += gridDim.x.  In: lanes run along U, row c of the source goes to
+//     tile[ul][c], so LDS holds the slab in output order.  Out, after a
+//     barrier: a lane owns aligned 16-byte windows of the slab's byte range
+//     (the transpose path's window arithmetic on one long row), splits its
+//     first element index into (ul, c) with one 32-bit division by the
+//     wave-uniform szC and walks LDS element by element with a carry at the
+//     row end, as DIRECT walks the source.  Whole windows are one aligned
+//     16-byte store and checksum_add, the slab's head and tail go out per
+//     element, the owner of the tensor's last element stores the padding.
+//     LDS row pitch: for elements up to 4 bytes the row's bytes rounded up
+//     to whole words and then to an ODD number of words; for 8 and 16 bytes
+//     an odd number of elements (szC | 1), which keeps them naturally
+//     aligned.  In the load phase lanes are one pitch apart at the same c.
+//     An odd word pitch times 0..63 is a bijection on any power-of-two bank
+//     count, so 4-byte writes are conflict-free for odd and for even szC
+//     (even szC pays one pad word per row, odd szC none); 1- and 2-byte
+//     lanes sit at the same byte of their own words, in distinct banks, the
+//     same way; 8- and 16-byte writes are served per half and quarter wave,
+//     where an odd element pitch again maps lanes to distinct bank groups.
+//     The store phase reads with lanes 16 output bytes, four words and now
+//     and then a pad, apart: a 4-way conflict on each element read.  At 4, 8
+//     and 16 bytes that equals the four passes one 128-bit read of the
+//     window takes; at 2 and 1 bytes a window costs 8 and 16 such reads,
+//     which is the price of one element per access.  At most
+//     256 rows * 36 bytes = 9 KiB (1 byte, szC 31); 7.75 KiB from 4 bytes up.
+//     Two neighbours stay on DIRECT even when SLAB is forced: a U that is not
+//     adjacent to C, where a slab is not contiguous in the output, and a U
+//     shorter than kGatherTransposeMin, such as the I = 3 of a first
+//     convolution, where a source row would fill an eighth of a wave's load or
+//     less.  That second threshold is reasoned, not measured, like the first.
+//     Measured (profiles/short_inner_results.md, (512, 512, 3, 3)
+//     channels_last): the kernel takes 0.034 ms in bf16 and 0.035 ms in
+//     float32 where DIRECT takes 0.019 and 0.024 ms, far outside the spread.
+//     A slab is 2304 bytes of output: two barriers, the coordinate divisions
+//     and a full round trip to HBM are paid per 2.3 KiB, where a DIRECT tile
+//     is 16 KiB with 32 loads in flight per lane.  So gather_plan keeps these
+//     tensors on DIRECT for every element size (1, 8 and 16 bytes are not
+//     measured and get no benefit of the doubt).
 //
-// Both paths end like the other checksum kernels: wave shuffles, LDS, one
+// All paths end like the other checksum kernels: wave shuffles, LDS, one
 // atomicAdd pair per workgroup.  The source is only read; no byte outside
 // [dst, dst + dst_bytes) is written.  This is pure data movement: there is no
 // product to accumulate, so the matrix (MFMA) instructions have nothing to do
 // here and are not used.
 //
 // Resources (-Rpass-analysis=kernel-resource-usage, gfx950): no scratch in
-// any instantiation; the figures are in profiles/strided_results.md.
+// any instantiation; the figures are in profiles/strided_results.md and, for
+// SLAB, in profiles/short_inner_results.md.
 struct GatherParams {
     const unsigned char* src;
     unsigned char* dst;
@@ -3070,7 +3122,9 @@ struct GatherParams {
     // stride[i] - size[i + 1] * stride[i + 1] modulo 2^64
     unsigned long long carry[3];
     // transpose path: C is dimension 3, U the unit-stride one, R0 and R1 the
-    // other two in order; ss = source stride, os = output stride, in elements
+    // other two in order; ss = source stride, os = output stride, in elements.
+    // The slab path uses the same fields: its U is dimension 2, osU == szC,
+    // nU counts slabs along U, nC is 1 and npatch the slabs in all
     unsigned long long szU, szC, ssC, osU;
     unsigned long long szR1, ssR0, ssR1, osR0, osR1;
     unsigned long long nU, nC, npatch;  // patches along U, along C, in all
@@ -3263,7 +3317,125 @@ __device__ __forceinline__ void gather_transpose(const GatherParams& p, unsigned
         gather_transpose_patch<ES>(p, tile, patch, 0ull, s0, t);
 }
 
-// MODE 0: direct, 32-bit element indices; 1: direct, 64-bit; 2: transpose
+template <int ES> struct GatherSlab {
+    static constexpr int TU = 256 / ES;  // a source row of a slab is 256 bytes
+    static constexpr unsigned int kMaxC = 31;  // szC < kGatherTransposeMin
+    // bytes per LDS row of szc elements: an odd number of words up to 4-byte
+    // elements, an odd number of elements above
+    static __host__ __device__ constexpr unsigned int pitch(unsigned int szc) {
+        return ES >= 8 ? (szc | 1u) * ES : (((szc * ES + 3u) / 4u) | 1u) * 4u;
+    }
+    static constexpr int kBytes = TU * pitch(kMaxC);
+};
+
+// One slab of the slab path through `tile` (GatherSlab<ES>::kBytes of LDS,
+// 16-byte aligned), which is free again when this returns.  base: as for
+// gather_transpose_patch.
+template <int ES>
+__device__ __forceinline__ void gather_slab_unit(const GatherParams& p, unsigned char* tile,
+                                                 unsigned long long slab,
+                                                 unsigned long long base,
+                                                 unsigned long long& s0,
+                                                 unsigned long long& t) {
+    typedef typename GatherElem<ES>::type T;
+    constexpr int EPV = 16 / ES;
+    constexpr unsigned int TU = GatherSlab<ES>::TU;
+    const unsigned long long data_bytes = p.numel * ES;
+    // the slab's coordinates: wave-uniform, from the slab index alone.  A slab
+    // holds at least 64 elements and dst_bytes stays at or below 16 GiB, so
+    // the slab index, nU and szR1 are below 2^28: 32-bit divisions
+    const unsigned int nU = (unsigned int)p.nU, szR1 = (unsigned int)p.szR1;
+    const unsigned int pu = (unsigned int)slab % nU, r = (unsigned int)slab / nU;
+    const unsigned long long r1 = r % szR1, r0 = r / szR1;
+    const unsigned long long u0 = (unsigned long long)pu * TU;
+    const unsigned int nu = (unsigned int)(p.szU - u0 < TU ? p.szU - u0 : TU);
+    const unsigned int szc = (unsigned int)p.szC;  // 2 .. kMaxC: the host's rule
+    const unsigned int pitch = GatherSlab<ES>::pitch(szc);
+    const unsigned long long ssC = p.ssC;
+    const CSP_GLOBAL T* __restrict__ src =
+        (const CSP_GLOBAL T*)p.src + (r0 * p.ssR0 + r1 * p.ssR1 + u0);
+    CSP_GLOBAL unsigned char* const dst = (CSP_GLOBAL unsigned char*)p.dst;
+    // the slab's first output byte and its length: at most 256 * kMaxC
+    const unsigned long long a = (r0 * p.osR0 + r1 * p.osR1 + u0 * szc) * ES;
+    const unsigned int slab_bytes = nu * szc * ES;
+
+    // in: lanes along U, up to six loads in flight per lane before the first
+    // LDS write for 1 and 2 bytes, four for 4 and 8, two for 16: a 3 x 3 slab
+    // of 2 bytes or more is loaded in one round.  More in flight costs the
+    // packed kernel its fourth wave per SIMD
+    constexpr int BATCH = ES <= 2 ? 6 : ES <= 8 ? 4 : 2;
+    const unsigned int cells = TU * szc;
+    for (unsigned int i0 = threadIdx.x; i0 < cells; i0 += BATCH * 256) {
+        T e[BATCH] = {};
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j) {
+            const unsigned int i = i0 + 256 * j, ul = i % TU, c = i / TU;
+            if (i < cells && ul < nu) e[j] = src[ul + c * ssC];
+        }
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j) {
+            const unsigned int i = i0 + 256 * j, ul = i % TU, c = i / TU;
+            if (i < cells && ul < nu) *reinterpret_cast<T*>(tile + ul * pitch + c * ES) = e[j];
+        }
+    }
+    __syncthreads();
+
+    // out: the slab is one run of slab_bytes output bytes from a; it touches
+    // `slots` aligned 16-byte windows, every one of them in at least a byte
+    const unsigned int slots = ((unsigned int)(a & 15u) + slab_bytes + 15u) / 16u;
+    const unsigned int gap = pitch - szc * ES;  // from a row's end to the next row
+    for (unsigned int i = threadIdx.x; i < slots; i += 256) {
+        const unsigned long long w = (a & ~15ull) + 16ull * i;
+        const unsigned long long lo = a > w ? a : w;
+        const unsigned long long hi = a + slab_bytes < w + 16 ? a + slab_bytes : w + 16;
+        const unsigned int e0 = (unsigned int)(lo - a) / ES;  // first element, in the slab
+        const unsigned int ul = e0 / szc;
+        unsigned int c = e0 - ul * szc;
+        const unsigned char* q = tile + ul * pitch + c * ES;
+        if (hi - lo == 16) {
+            u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < EPV; ++k) {
+                gather_put<ES>(v, k, *reinterpret_cast<const T*>(q));
+                if constexpr (EPV > 1) {  // on to the next element, with carry
+                    q += ES;
+                    if (++c == szc) {
+                        c = 0;
+                        q += gap;
+                    }
+                }
+            }
+            *(CSP_GLOBAL u32x4*)(dst + lo) = v;
+            checksum_add(s0, t, v, (unsigned int)((base + lo) >> 2));
+        } else if constexpr (ES < 16) {  // a 16-byte element is always a whole window
+            for (unsigned long long b = lo; b < hi; b += ES) {
+                const T e = *reinterpret_cast<const T*>(q);
+                *(CSP_GLOBAL T*)(dst + b) = e;
+                gather_sum_elem<ES>(s0, t, e, base + b);
+                q += ES;
+                if (++c == szc) {
+                    c = 0;
+                    q += gap;
+                }
+            }
+            if (hi == data_bytes)  // the last element: its owner stores the padding
+                for (unsigned long long b = hi; b < p.dst_bytes; b += ES)
+                    *(CSP_GLOBAL T*)(dst + b) = (T)0;
+        }
+    }
+    __syncthreads();  // the tile is free for the next slab
+}
+
+template <int ES>
+__device__ __forceinline__ void gather_slab(const GatherParams& p, unsigned long long& s0,
+                                            unsigned long long& t) {
+    __shared__ __attribute__((aligned(16))) unsigned char tile[GatherSlab<ES>::kBytes];
+    for (unsigned long long slab = blockIdx.x; slab < p.npatch; slab += gridDim.x)
+        gather_slab_unit<ES>(p, tile, slab, 0ull, s0, t);
+}
+
+// MODE 0: direct, 32-bit element indices; 1: direct, 64-bit; 2: transpose;
+// 3: slab
 template <int ES, int MODE>
 __global__ __launch_bounds__(256) void csp_gather_checksum_kernel(
     GatherParams p, unsigned long long* __restrict__ out) {
@@ -3274,7 +3446,8 @@ __global__ __launch_bounds__(256) void csp_gather_checksum_kernel(
         gather_direct<ES, unsigned int>(p, blockIdx.x, gridDim.x, ntiles, 0u, s0, t);
     else if constexpr (MODE == 1)
         gather_direct<ES, unsigned long long>(p, blockIdx.x, gridDim.x, ntiles, 0u, s0, t);
-    else gather_transpose<ES>(p, s0, t);
+    else if constexpr (MODE == 2) gather_transpose<ES>(p, s0, t);
+    else gather_slab<ES>(p, s0, t);
     unsigned long long s1 = t + s0;
 
     for (int off = 32; off > 0; off >>= 1) {
@@ -3300,7 +3473,8 @@ template <int ES>
 static gather_fn gather_variant_of(int mode) {
     if (mode == 0) return csp_gather_checksum_kernel<ES, 0>;
     if (mode == 1) return csp_gather_checksum_kernel<ES, 1>;
-    return csp_gather_checksum_kernel<ES, 2>;
+    if (mode == 2) return csp_gather_checksum_kernel<ES, 2>;
+    return csp_gather_checksum_kernel<ES, 3>;
 }
 
 static gather_fn gather_variant(unsigned int es, int mode) {
@@ -3318,12 +3492,17 @@ static gather_fn gather_variant(unsigned int es, int mode) {
 // a row of the coalesced load covers 128 bytes of 4-byte elements.  Below
 // it most of a patch's LDS slots and both of its barriers serve nothing, and
 // the direct path's strided loads find their neighbours in the caches.
-// Reasoned, not measured.
+// Reasoned, not measured.  A C below it may go to the slab path when U lies
+// directly above it and holds at least as many elements: the same figure,
+// for the same reason on the load side (half of a 256-byte source row at
+// 4 bytes), and reasoned, not measured, as well.
 static const uint64_t kGatherTransposeMin = 32;
+static_assert(GatherSlab<1>::kMaxC + 1 == kGatherTransposeMin, "the slab's LDS bound");
 
 #define CSP_GATHER_PATH_DIRECT 1     // per-element loads
 #define CSP_GATHER_PATH_DIRECT16 2   // the direct kernel on 16-byte elements
 #define CSP_GATHER_PATH_TRANSPOSE 3  // LDS tile
+#define CSP_GATHER_PATH_SLAB 5       // LDS slab in output order (4 is CSP_GATHER_PATH_COPY)
 
 // At most 1024 blocks, the cap of the other kernels that carry a checksum.
 static const size_t kGatherGridCapDefault = 1024;
@@ -3340,9 +3519,11 @@ extern "C" size_t csp_gather_checksum_grid_cap(size_t cap) {
 
 // Tools only: 0 leaves the path of the next csp_gather_checksum_dev calls to
 // the host's choice, 1 forces the direct path, so that a test can run both
-// paths on one input.  Returns the value in effect.
+// paths on one input, 2 takes the slab path wherever its rule holds (the host
+// does not choose it by itself: see gather_plan) and leaves every other
+// choice alone.  Returns the value in effect.
 extern "C" int csp_gather_checksum_path(int force) {
-    g_gather_force_path = force == 1 ? 1 : 0;
+    g_gather_force_path = force == 1 || force == 2 ? force : 0;
     return g_gather_force_path;
 }
 
@@ -3426,20 +3607,31 @@ static bool gather_extent(int nd, const uint64_t* sz, const uint64_t* st, unsign
 // The path choice for the collapsed tensor (sz and st may be rewritten; p->src
 // and p->dst_bytes are set already): fills the rest of *p, the element size
 // the kernel runs at (*es_io: 16 on the 16-byte sub-path), the gather kernel's
-// MODE and the number of tiles or patches.  Returns one of CSP_GATHER_PATH_*.
-static int gather_plan(int nd, uint64_t* sz, uint64_t* st, uint64_t numel, bool force_direct,
+// MODE and the number of tiles, patches or slabs.  Returns one of
+// CSP_GATHER_PATH_*.  force: 0, or the tools' 1 (direct) or 2 (slab where its
+// rule holds).  The slab is withheld from the host's own choice for every
+// element size: it measured 1.8 (bf16) and 1.5 (float32) times slower than
+// the direct path on a (512, 512, 3, 3) channels_last weight, see
+// profiles/short_inner_results.md.
+static int gather_plan(int nd, uint64_t* sz, uint64_t* st, uint64_t numel, int force,
                        GatherParams* p, unsigned int* es_io, int* mode, size_t* work) {
+    const bool force_direct = force == 1;
     unsigned int es = *es_io;
     int path = CSP_GATHER_PATH_DIRECT;
-    const int unit = [&] {  // U: a dimension other than C with source stride 1
+    int unit = [&] {  // U: a dimension other than C with source stride 1
         for (int i = 0; i < nd - 1; ++i)
             if (st[i] == 1 && sz[i] >= kGatherTransposeMin) return i;
         return -1;
     }();
-    if (!force_direct && nd >= 2 && st[nd - 1] != 1 && sz[nd - 1] >= kGatherTransposeMin &&
-        unit >= 0) {
-        *mode = 2;
-        path = CSP_GATHER_PATH_TRANSPOSE;
+    // SLAB: a short C with U directly above it, so that U's output stride is szC
+    const bool slab = force == 2 && nd >= 2 && sz[nd - 1] >= 2 &&
+                      sz[nd - 1] < kGatherTransposeMin &&
+                      st[nd - 2] == 1 && sz[nd - 2] >= kGatherTransposeMin;
+    const bool transpose = nd >= 2 && sz[nd - 1] >= kGatherTransposeMin && unit >= 0;
+    if (!force_direct && nd >= 2 && st[nd - 1] != 1 && (slab || transpose)) {
+        if (slab) unit = nd - 2;
+        *mode = slab ? 3 : 2;
+        path = slab ? CSP_GATHER_PATH_SLAB : CSP_GATHER_PATH_TRANSPOSE;
         p->numel = numel;
         uint64_t os[4];  // output strides: row-major
         os[nd - 1] = 1;
@@ -3456,7 +3648,8 @@ static int gather_plan(int nd, uint64_t* sz, uint64_t* st, uint64_t numel, bool 
             else { p->ssR0 = st[i]; p->osR0 = os[i]; }
             ++rest;
         }
-        const uint64_t tu = es <= 4 ? 64 : 32, tc = 64;
+        // a slab holds all of C: GatherSlab<ES>::TU by szC
+        const uint64_t tu = slab ? 256 / es : es <= 4 ? 64 : 32, tc = slab ? p->szC : 64;
         p->nU = (p->szU + tu - 1) / tu;
         p->nC = (p->szC + tc - 1) / tc;
         p->npatch = (numel / (p->szU * p->szC)) * p->nU * p->nC;  // <= numel
@@ -3572,7 +3765,7 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
     unsigned int es = elem_size;
     int mode = 0;
     size_t work = 0;  // tiles or patches
-    const int path = gather_plan(nd, sz, st, numel, g_gather_force_path == 1, &p, &es, &mode,
+    const int path = gather_plan(nd, sz, st, numel, g_gather_force_path, &p, &es, &mode,
                                  &work);
 
     // one accumulator pair per process, one call at a time
@@ -3640,7 +3833,7 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
 // weight no longer cost one contiguous() (a launch, an allocation, a read and
 // a write) per tensor before the pack kernel starts.
 //
-// The host turns every non-empty segment into one table entry of one of three
+// The host turns every non-empty segment into one table entry of one of four
 // kinds and counts its work units; `unit_begin` is the strictly increasing
 // prefix of those counts.  A workgroup takes unit = blockIdx.x, += gridDim.x,
 // finds the entry by the pack kernel's binary search (the unit index alone
@@ -3653,13 +3846,18 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
 //     unit: gather_direct with 32-bit element indices (the host refuses
 //     2^32 elements), the 16-byte sub-path included;
 //   - TRANSPOSE: a strided source, one patch per unit through the LDS tile:
-//     gather_transpose_patch, the body of csp_gather_checksum_kernel.
+//     gather_transpose_patch, the body of csp_gather_checksum_kernel;
+//   - SLAB: a strided source with a short inner dimension, one slab per unit
+//     through the same LDS tile: gather_slab_unit, likewise shared.  The
+//     host makes no such entry by itself (the body measured slower than
+//     DIRECT, see gather_plan); csp_pack_gather_checksum_path(2) does.
 //
 // LDS: one tile of 33 792 bytes, what the 16-byte transpose needs, used by
-// TRANSPOSE units of every element size; with the 64 bytes of the final
-// reduction four workgroups per CU take 132.3 KiB of the 160 KiB.  COPY and
-// DIRECT units do not touch LDS at all, and a patch ends with the barrier that
-// frees the tile, so a unit of any kind may follow a patch in a workgroup.
+// TRANSPOSE units of every element size and by SLAB units, which need at
+// most 9 KiB of it; with the 64 bytes of the final reduction four workgroups
+// per CU take 132.3 KiB of the 160 KiB.  COPY and DIRECT units do not touch
+// LDS at all, and a patch or slab ends with the barrier that frees the tile,
+// so a unit of any kind may follow one in a workgroup.
 // The barriers sit inside the uniform branch: every lane of the workgroup
 // takes it.
 //
@@ -3671,10 +3869,12 @@ extern "C" int csp_gather_checksum_dev(const void* src, unsigned elem_size, unsi
 // are only read.  No MFMA: nothing is multiplied.
 //
 // Resources (-Rpass-analysis=kernel-resource-usage, gfx950): no scratch, no
-// spills; the figures are in profiles/packed_strided_results.md.
+// spills; the figures are in profiles/packed_strided_results.md and, since
+// SLAB, in profiles/short_inner_results.md.
 #define CSP_PACK_GATHER_COPY 0
 #define CSP_PACK_GATHER_DIRECT 1
 #define CSP_PACK_GATHER_TRANSPOSE 2
+#define CSP_PACK_GATHER_SLAB 3
 
 #define CSP_GATHER_PATH_COPY 4  // path_out of a contiguous segment
 
@@ -3695,6 +3895,12 @@ static_assert(kPackGatherTileBytes >= GatherTile<8>::TC * GatherTile<8>::PITCH &
               kPackGatherTileBytes >= GatherTile<2>::TC * GatherTile<2>::PITCH &&
               kPackGatherTileBytes >= GatherTile<1>::TC * GatherTile<1>::PITCH,
               "the tile serves every element size");
+static_assert(kPackGatherTileBytes >= GatherSlab<16>::kBytes &&
+              kPackGatherTileBytes >= GatherSlab<8>::kBytes &&
+              kPackGatherTileBytes >= GatherSlab<4>::kBytes &&
+              kPackGatherTileBytes >= GatherSlab<2>::kBytes &&
+              kPackGatherTileBytes >= GatherSlab<1>::kBytes,
+              "the tile holds a slab of every element size");
 static_assert(4 * (kPackGatherTileBytes + 64) <= 160 * 1024, "four workgroups per CU");
 
 __global__ __launch_bounds__(256) void csp_pack_gather_checksum_kernel(
@@ -3736,6 +3942,12 @@ __global__ __launch_bounds__(256) void csp_pack_gather_checksum_kernel(
             else if (es == 4) gather_direct<4, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
             else if (es == 2) gather_direct<2, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
             else gather_direct<1, unsigned int, true>(p, u, 1, u + 1, word_base, s0, t);
+        } else if (kind == CSP_PACK_GATHER_SLAB) {
+            if (es == 16) gather_slab_unit<16>(p, tile, u, dst_off, s0, t);
+            else if (es == 8) gather_slab_unit<8>(p, tile, u, dst_off, s0, t);
+            else if (es == 4) gather_slab_unit<4>(p, tile, u, dst_off, s0, t);
+            else if (es == 2) gather_slab_unit<2>(p, tile, u, dst_off, s0, t);
+            else gather_slab_unit<1>(p, tile, u, dst_off, s0, t);
         } else {
             if (es == 16) gather_transpose_patch<16>(p, tile, u, dst_off, s0, t);
             else if (es == 8) gather_transpose_patch<8>(p, tile, u, dst_off, s0, t);
@@ -3778,10 +3990,11 @@ extern "C" size_t csp_pack_gather_checksum_grid_cap(size_t cap) {
 }
 
 // Tools only: 1 makes the next csp_pack_gather_checksum_dev calls take DIRECT
-// where the host would choose TRANSPOSE, 0 restores the host's choice.
-// Returns the value in effect.
+// where the host would choose TRANSPOSE, 2 makes them take SLAB wherever its
+// rule holds (the host does not choose it by itself: see gather_plan), 0
+// restores the host's choice.  Returns the value in effect.
 extern "C" int csp_pack_gather_checksum_path(int force) {
-    g_pack_gather_force_path = force == 1 ? 1 : 0;
+    g_pack_gather_force_path = force == 1 || force == 2 ? force : 0;
     return g_pack_gather_force_path;
 }
 
@@ -3956,9 +4169,11 @@ extern "C" int csp_pack_gather_checksum_dev(const CspPackGatherSeg* segs, size_t
             int mode = 0;
             size_t work = 0;
             e.es = g.elem_size;
-            paths[k] = gather_plan(nd, sz, st, numel, g_pack_gather_force_path == 1, &e.g, &e.es,
+            paths[k] = gather_plan(nd, sz, st, numel, g_pack_gather_force_path, &e.g, &e.es,
                                    &mode, &work);
-            e.kind = mode == 2 ? CSP_PACK_GATHER_TRANSPOSE : CSP_PACK_GATHER_DIRECT;
+            e.kind = mode == 3   ? CSP_PACK_GATHER_SLAB
+                     : mode == 2 ? CSP_PACK_GATHER_TRANSPOSE
+                                 : CSP_PACK_GATHER_DIRECT;
             units += work;
         }
         table.push_back(e);

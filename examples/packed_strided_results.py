@@ -10,12 +10,15 @@ per non-contiguous tensor.
 Needs one MI355X and the built libraries (``python -m
 covalent_ssh_plugin_amd.ops.build``).  ``--measure`` times
 ``csp_pack_gather_checksum_dev`` against ``contiguous()`` per tensor followed
-by ``csp_pack_checksum_dev`` (the path before it) on two fixed workloads: one
-warm round first, then 5 alternating repetitions, medians with all values.
+by ``csp_pack_checksum_dev`` (the path before it) and against the same call
+with the slab path allowed (the tools' force value 2) on five fixed workloads: one warm round first,
+then 5 alternating repetitions, medians with all values.  ``--parent-lib``
+adds the same call through another build of the library.
 """
 
 import argparse
 import asyncio
+import importlib.util
 import statistics
 import sys
 import tempfile
@@ -54,6 +57,16 @@ def channels_last_state_dict(dtype, device="cuda"):
     return out
 
 
+def conv3x3_state_dict(dtype, device="cuda"):
+    """Only the 3 x 3 weights of the stack, in channels_last: every tensor has
+    a 9-element inner dimension under the unit-stride one."""
+    return {
+        "conv%d.weight" % k: torch.randn(*shape, device=device).to(dtype).to(
+            memory_format=torch.channels_last)
+        for k, shape in enumerate(CONVS) if shape[2:] == (3, 3)
+    }
+
+
 def transposed_linears(device="cuda"):
     return {
         "fc%d.weight_t" % k: torch.randn(*shape, device=device).t()
@@ -64,6 +77,8 @@ def transposed_linears(device="cuda"):
 WORKLOADS = {
     "channels_last state dict, bf16": lambda: channels_last_state_dict(torch.bfloat16),
     "channels_last state dict, f32": lambda: channels_last_state_dict(torch.float32),
+    "3 x 3 channels_last weights only, bf16": lambda: conv3x3_state_dict(torch.bfloat16),
+    "3 x 3 channels_last weights only, f32": lambda: conv3x3_state_dict(torch.float32),
     "transposed Linear weights, f32": transposed_linears,
 }
 
@@ -78,8 +93,9 @@ def layout(tensors):
     return sizes, offsets, total
 
 
-def packed_gather(tensors, arena):
-    """The new call: strided tensors stay as they are."""
+def packed_gather(tensors, arena, lib=probe, force=0):
+    """The new call: strided tensors stay as they are.  ``force`` 2 takes the
+    slab path, which the host does not choose by itself, where its rule holds."""
     sizes, offsets, total = layout(tensors)
     segments = [
         (t.data_ptr(), off, n) if t.is_contiguous()
@@ -87,7 +103,11 @@ def packed_gather(tensors, arena):
         for t, off, n in zip(tensors, offsets, sizes)
     ]
     torch.cuda.synchronize()
-    return probe.pack_gather_checksum_device(segments, arena.data_ptr(), total)
+    lib.pack_gather_checksum_path(force)
+    try:
+        return lib.pack_gather_checksum_device(segments, arena.data_ptr(), total)
+    finally:
+        lib.pack_gather_checksum_path(0)
 
 
 def before(tensors, arena):
@@ -116,19 +136,28 @@ def copy_rate(nbytes=256 << 20):
     return 2 * nbytes / statistics.median(times)
 
 
-def measure():
+def measure(parent_lib=""):
     """Host time of the calls as the worker sees them, synchronisation
     included, alternating; and the new kernel alone."""
     rate = copy_rate()
+    others = {"slab forced": (probe, 2)}
+    if parent_lib:  # a second copy of the bindings, bound to the other build
+        spec = importlib.util.spec_from_file_location("probe_parent", probe.__file__)
+        other = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(other)
+        other.load(parent_lib)
+        others["parent library"] = (other, 0)
     print("| workload | tensors (strided) | arena bytes | strided bytes | paths | new ms "
-          "| before ms | spread of before | new kernel ms | floor new / before ms |")
-    print("|---|---|---|---|---|---|---|---|---|---|")
+          "| before ms | spread of before | new kernel ms | floor new / before ms | "
+          + " | ".join("%s ms | %s kernel ms" % (name, name) for name in others) + " |")
+    print("|---|---|---|---|---|---|---|---|---|---|" + "---|---|" * len(others))
     for label, make in WORKLOADS.items():
         tensors = list(make().values())
         sizes, _, total = layout(tensors)
         strided = sum(n for t, n in zip(tensors, sizes) if not t.is_contiguous())
         arena = torch.empty(total, dtype=torch.uint8, device="cuda")
         rows = {"new": [], "before": [], "kernel": []}
+        rows.update({name: ([], []) for name in others})
         for rep in range(REPS + 1):  # the first round warms
             t0 = time.perf_counter()
             report = packed_gather(tensors, arena)
@@ -136,16 +165,25 @@ def measure():
             sums = before(tensors, arena)["sum"]
             t2 = time.perf_counter()
             assert report["sums"] == sums, (label, report["sums"], sums)
+            for name, (lib, force) in others.items():
+                t3 = time.perf_counter()
+                again = packed_gather(tensors, arena, lib, force)
+                t4 = time.perf_counter()
+                assert again["sums"] == sums, (label, name, again["sums"], sums)
+                if rep:
+                    rows[name][0].append((t4 - t3) * 1e3)
+                    rows[name][1].append(again["kernel_ms"])
             if rep:
                 rows["new"].append((t1 - t0) * 1e3)
                 rows["before"].append((t2 - t1) * 1e3)
                 rows["kernel"].append(report["kernel_ms"])
         paths = {p: report["paths"].count(p) for p in sorted(set(report["paths"]))}
-        print("| %s | %d (%d) | %d | %d | %s | %s | %s | %.4g | %s | %.4g / %.4g |" % (
+        print("| %s | %d (%d) | %d | %d | %s | %s | %s | %.4g | %s | %.4g / %.4g | %s |" % (
             label, len(tensors), sum(not t.is_contiguous() for t in tensors), total, strided,
             " ".join("%s:%d" % kv for kv in paths.items()), fmt(rows["new"]),
             fmt(rows["before"]), max(rows["before"]) - min(rows["before"]), fmt(rows["kernel"]),
-            2 * total / rate, 2 * (total + strided) / rate))
+            2 * total / rate, 2 * (total + strided) / rate,
+            " | ".join("%s | %s" % (fmt(rows[name][0]), fmt(rows[name][1])) for name in others)))
         del tensors, arena
         torch.cuda.empty_cache()
 
@@ -180,8 +218,9 @@ async def demo():
 if __name__ == "__main__":
     parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     parser.add_argument("--measure", action="store_true")
+    parser.add_argument("--parent-lib", default="", help="another build of libcsp_gpu.so")
     opts = parser.parse_args()
     if opts.measure:
-        measure()
+        measure(opts.parent_lib)
     else:
         asyncio.run(demo())

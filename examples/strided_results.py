@@ -4,6 +4,8 @@ the worker lays it out with one checksummed gather kernel, where torch's
 
     python examples/strided_results.py            # one round trip, with the stats
     python examples/strided_results.py --measure  # the tables of profiles/strided_results.md
+    python examples/strided_results.py --measure-short-inner [--parent-lib libcsp_gpu.so]
+                                                  # those of profiles/short_inner_results.md
 
 Needs one MI355X and the built libraries (``python -m
 covalent_ssh_plugin_amd.ops.build``).  ``--measure`` times
@@ -11,10 +13,15 @@ covalent_ssh_plugin_amd.ops.build``).  ``--measure`` times
 ``csp_pack_checksum_dev`` (the path before the option) on six layouts, and the
 round trip of a 256 MiB transposed result with the option on against off: one
 warm call first, then 5 alternating repetitions, medians with all values.
+``--measure-short-inner`` times the slab path (tools' force value 2) on a ``(512, 512, 3, 3)``
+``channels_last`` weight in bf16 and float32 against the host's choice, the direct path,
+against ``csp_copy_checksum_dev`` on the same byte count and, with
+``--parent-lib``, against another build of the library on the same input.
 """
 
 import argparse
 import asyncio
+import importlib.util
 import statistics
 import sys
 import tempfile
@@ -43,6 +50,14 @@ SHAPES = {
         64, 256, 56, 56, device="cuda", dtype=torch.bfloat16
     ).contiguous(memory_format=torch.channels_last),
 }
+
+
+# 3 x 3 weights: after collapsing (512, 512, 9) with strides (4608, 1, 512)
+SHORT_INNER = {
+    "(512, 512, 3, 3) bf16 channels_last": torch.bfloat16,
+    "(512, 512, 3, 3) f32 channels_last": torch.float32,
+}
+CALLS = 20  # a value of the short-inner table is the mean of this many calls
 
 
 def transposed(n):
@@ -128,7 +143,7 @@ def measure_kernel():
             t2 = time.perf_counter()
             assert report["sums"] == sums, (label, report, sums)
             forced = None
-            if report["path"] == "transpose":
+            if report["path"] in ("transpose", "slab"):
                 probe.gather_checksum_path(1)
                 t3 = time.perf_counter()
                 forced = gather(t, master, nbytes)
@@ -148,6 +163,61 @@ def measure_kernel():
             fmt(rows["direct"]) if rows["direct"] else ""))
         del t, master
         torch.cuda.empty_cache()
+
+
+def measure_short_inner(parent_lib=""):
+    """The slab path (force value 2) against the host's choice (direct), the copy with
+    checksum of as many bytes, and optionally the library at ``parent_lib``:
+    host time per call and the kernel alone, alternating within one process."""
+    variants = {"slab forced": (probe, 2), "host's choice": (probe, 0)}
+    if parent_lib:  # a second copy of the bindings, bound to the other build
+        spec = importlib.util.spec_from_file_location("probe_parent", probe.__file__)
+        other = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(other)
+        other.load(parent_lib)
+        variants["parent"] = (other, 0)
+    print("| layout | bytes | variant | path | call ms | kernel ms | call / copy | spread of call |")
+    print("|---|---|---|---|---|---|---|---|")
+    for label, dtype in SHORT_INNER.items():
+        t = torch.randn(512, 512, 3, 3, device="cuda").to(dtype).contiguous(
+            memory_format=torch.channels_last)
+        nbytes = t.numel() * t.element_size()
+        flat = t.contiguous().view(torch.uint8)
+        master = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        rows = {name: ([], []) for name in variants}
+        copies, paths, sums = [], {}, set()
+        for rep in range(REPS + 1):  # the first round warms
+            for name, (lib, force) in variants.items():
+                lib.gather_checksum_path(force)
+                kernel = 0.0
+                t0 = time.perf_counter()
+                for _ in range(CALLS):
+                    report = lib.gather_checksum_device(
+                        t.data_ptr(), t.element_size(), list(t.shape), list(t.stride()),
+                        master.data_ptr(), nbytes)
+                    kernel += report["kernel_ms"]
+                call = (time.perf_counter() - t0) * 1e3 / CALLS
+                lib.gather_checksum_path(0)
+                paths[name] = report["path"]
+                sums.add(report["sums"])
+                if rep:
+                    rows[name][0].append(call)
+                    rows[name][1].append(kernel / CALLS)
+            t0 = time.perf_counter()
+            for _ in range(CALLS):
+                sums.add(probe.copy_checksum_device(master.data_ptr(), flat.data_ptr(), nbytes))
+            if rep:
+                copies.append((time.perf_counter() - t0) * 1e3 / CALLS)
+        assert len(sums) == 1, (label, sums)
+        assert torch.equal(master, flat.reshape(-1))
+        floor = statistics.median(copies)
+        print("| %s | %d | copy with checksum | | %s | | 1 | %.4g |" % (
+            label, nbytes, fmt(copies), max(copies) - min(copies)))
+        for name, (calls, kernels) in rows.items():
+            print("| %s | %d | %s | %s | %s | %s | %.3g | %.4g |" % (
+                label, nbytes, name, paths[name], fmt(calls), fmt(kernels),
+                statistics.median(calls) / floor, max(calls) - min(calls)))
 
 
 async def measure_round_trip(n=8192):
@@ -208,9 +278,14 @@ async def demo():
 if __name__ == "__main__":
     parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     parser.add_argument("--measure", action="store_true")
+    parser.add_argument("--measure-short-inner", action="store_true")
+    parser.add_argument("--parent-lib", default="", help="another build of libcsp_gpu.so")
     opts = parser.parse_args()
-    if opts.measure:
+    if opts.measure_short_inner:
+        measure_short_inner(opts.parent_lib)
+    elif opts.measure:
         measure_kernel()
+        measure_short_inner(opts.parent_lib)
         asyncio.run(measure_round_trip())
         asyncio.run(hbm_footprint())
     else:
