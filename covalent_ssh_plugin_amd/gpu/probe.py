@@ -32,6 +32,9 @@ gfx950 only) provides:
   and strided tensors together by one launch, with its checksum
   (``pack_tensor_results`` with ``gather_tensor_results``), and
   ``csp_gather_supported``, the host-side question whether a layout is served,
+* ``csp_narrow_checksum_dev`` — a contiguous float32, float64, int32 or int64
+  device tensor tested for a lossless narrower form, written in that form and
+  checksummed by one launch (``narrow_tensor_results``),
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
   ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
@@ -246,6 +249,20 @@ def load(path: str = "") -> ctypes.CDLL:
     lib.csp_diff_block_bytes.argtypes = []
     lib.csp_diff_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_diff_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_narrow_checksum_dev.restype = ctypes.c_int
+    lib.csp_narrow_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_int,
+        ctypes.c_int,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_float),
+    ]
+    lib.csp_narrow_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_narrow_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_gather_checksum_dev.restype = ctypes.c_int
     lib.csp_gather_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -723,6 +740,70 @@ def diff_checksum_grid_cap(cap: int = 0) -> int:
     """Tools only: set the grid cap of :func:`diff_checksum_device` (0
     restores the shipped default).  Returns the cap in effect."""
     return int(load().csp_diff_checksum_grid_cap(int(cap)))
+
+
+# element kinds of :func:`narrow_checksum_device`, by torch dtype name, their
+# sizes, and every source's targets from the narrowest to the widest
+NARROW_KINDS = {
+    "float32": 0, "float64": 1, "int32": 2, "int64": 3, "bfloat16": 4, "int16": 5, "uint8": 6,
+}
+NARROW_ELEM_SIZE = {
+    "float32": 4, "float64": 8, "int32": 4, "int64": 8, "bfloat16": 2, "int16": 2, "uint8": 1,
+}
+NARROW_TARGETS = {
+    "float32": ("bfloat16",),
+    "float64": ("float32",),
+    "int64": ("uint8", "int16", "int32"),
+    "int32": ("uint8", "int16"),
+}
+
+
+def narrow_bytes(numel: int, dst: str) -> int:
+    """Bytes of ``numel`` elements narrowed to ``dst``, zero padded to 16."""
+    return (numel * NARROW_ELEM_SIZE[dst] + 15) // 16 * 16
+
+
+def narrow_checksum_device(
+    src_ptr: int, numel: int, src: str, dst: str = "", dst_ptr: int = 0, dst_bytes: int = 0
+) -> dict:
+    """Test the ``numel`` contiguous ``src`` elements (a dtype name of
+    ``NARROW_TARGETS``) at device pointer ``src_ptr`` for lossless narrowing
+    (``narrow_tensor_results``).  Returns ``{"rc", "fits", "sum",
+    "kernel_ms"}``; ``fits`` is the tuple of ``src``'s targets, narrowest
+    first, that give every element back bit for bit when widened.  With
+    ``dst_ptr`` 0 the call is a probe and stores nothing.  With ``dst_ptr``
+    set, the elements narrowed to ``dst`` are written there in the same kernel
+    launch, zero padded to ``dst_bytes == narrow_bytes(numel, dst)``, and
+    ``sum`` equals ``checksum_device(dst_ptr, dst_bytes)`` if ``dst`` is in
+    ``fits``; if it is not, the buffer and ``sum`` mean nothing.  An unserved
+    pair, a null or misaligned pointer, a wrong ``dst_bytes``, a source above
+    16 GiB or overlapping buffers raise ``GpuLibError`` and launch nothing.
+    Runs on the library's copy stream; a source written on another stream
+    must be complete first."""
+    lib = load()
+    out = (ctypes.c_uint64 * 2)()
+    fits = ctypes.c_uint32()
+    kernel_ms = ctypes.c_float()
+    rc = lib.csp_narrow_checksum_dev(
+        ctypes.c_void_p(src_ptr or None), numel, NARROW_KINDS.get(src, -1),
+        NARROW_KINDS.get(dst, -1), ctypes.c_void_p(dst_ptr or None), dst_bytes, out,
+        ctypes.byref(fits), ctypes.byref(kernel_ms),
+    )
+    _check(lib, rc, "csp_narrow_checksum_dev")
+    return {
+        "rc": rc,
+        "fits": tuple(
+            d for d in NARROW_TARGETS.get(src, ()) if fits.value >> NARROW_KINDS[d] & 1
+        ),
+        "sum": (int(out[0]), int(out[1])),
+        "kernel_ms": kernel_ms.value,
+    }
+
+
+def narrow_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`narrow_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_narrow_checksum_grid_cap(int(cap)))
 
 
 GATHER_PATHS = {0: "none", 1: "direct", 2: "direct16", 3: "transpose", 5: "slab"}

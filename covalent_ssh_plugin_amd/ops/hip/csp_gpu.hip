@@ -4263,6 +4263,462 @@ extern "C" int csp_pack_gather_checksum_dev(const CspPackGatherSeg* segs, size_t
     return done(0);
 }
 
+// ---------------------------------------------------------------------------
+// Lossless narrowing with checksum: a wide result sent at the width it needs
+// ---------------------------------------------------------------------------
+//
+// A float32 tensor that came out of a bf16 computation, an int64 tensor of
+// token ids, a float64 tensor of widened float32 values: each can cross the
+// pipe at a half, a quarter or an eighth of its bytes and be widened back
+// bit for bit.  Whether a tensor is such a case is known only after reading
+// all of it, which is what this kernel does, once: it tests every element
+// for exactness, writes the narrowed bytes and computes csp_checksum_dev of
+// those bytes in the same pass.
+//
+// Exactness is decided on the element's bits, by integer rules; no
+// conversion instruction and no denormal mode takes part:
+//
+//   - f32 -> bf16: exact iff the low 16 bits are zero; the value is bits >> 16;
+//   - f64 -> f32: exact iff the low 29 mantissa bits are zero and the value
+//     is +-0, has an exponent in the f32 normal range, is +-inf, or is a NaN
+//     with the quiet bit set.  Values in the f32 subnormal range and
+//     signalling NaNs are refused: the first keeps the rule free of rounding
+//     cases, the second is what a CPU widening would not give back.  The
+//     value is sign, re-biased exponent, mantissa >> 29;
+//   - integers: a signed target is exact iff sign-extending the low bytes
+//     gives the source, uint8 iff 0 <= x <= 255; the value is the low bytes.
+//
+// Every lane ORs what speaks against exactness into one u64 `bad` word, and
+// the host reads every target's verdict from it: for floats the bits that
+// had to be zero (bit 63: wrong class of value), for integers the OR of
+// x ^ (x >> 63), whose highest set bit is the width the magnitudes need, and
+// in bit 63 the OR of the signs.
+//
+// Data movement.  The OUTPUT is cut like the pack kernel's: 16 KiB tiles,
+// 256-thread workgroups looping tile += gridDim.x, every output vector
+// stored once with an aligned nontemporal 16-byte store.  One output vector
+// is made of R = source bytes / target bytes source vectors.  A lane that
+// loaded the R vectors of its own output vector would give every load
+// instruction a stride of 16 * R bytes across the wave; instead the loads
+// are coalesced and the pieces change lanes through LDS:
+//
+//   - a wave owns 4 steps of a tile; a step is 64 output vectors (1 KiB) made
+//     from 64 * R source vectors.  Load k of a step takes source vector
+//     k * 64 + lane, nontemporal; all loads of a trip are issued before the
+//     first use.  A trip is two steps for R = 2 and one for R = 4 and 8: 4, 4
+//     and 8 loads per lane, the pack kernel's 64 bytes in flight where R
+//     allows it;
+//   - each source vector is narrowed in registers to its 16 / R byte piece
+//     and written to a wave-private 1 KiB LDS strip at its linear output
+//     position (k * 64 + lane) * 16 / R: ds_write_b64, b32 or b16, consecutive
+//     across the lanes, so no bank conflicts;
+//   - each lane reads back one b128 at lane * 16, sums it at its arena-global
+//     word index and stores it.  Only lanes of one wave share a strip, and a
+//     wave's LDS operations complete in order: a wave-scope fence orders
+//     them for the compiler, no workgroup barrier is needed.
+//
+// With dst == nullptr (a probe) a uniform branch skips narrowing, LDS, sums
+// and stores.  Edges: only source vectors wholly below numel are loaded
+// whole, the last partial one is read element by element into a zero-padded
+// vector (a zero is exact for every target and narrows to zero, which is the
+// output's padding), nothing past numel is read, nothing past dst_bytes is
+// written.  At most 1024 workgroups: the cap of the other checksum-carrying
+// kernels, carried over, not measured for this one.
+#define CSP_KIND_F32 0
+#define CSP_KIND_F64 1
+#define CSP_KIND_I32 2
+#define CSP_KIND_I64 3
+#define CSP_KIND_BF16 4
+#define CSP_KIND_I16 5
+#define CSP_KIND_U8 6
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+static const unsigned long long kNarrowFlag = 1ull << 63;
+
+// one f64 (lo, hi words) as f32 bits; `bad` gets what speaks against it
+__device__ __forceinline__ unsigned int narrow_f64(unsigned int lo, unsigned int hi,
+                                                   unsigned long long& bad) {
+    const unsigned int e = (hi >> 20) & 0x7FFu;
+    const unsigned int mhi = hi & 0xFFFFFu;  // the top 20 mantissa bits
+    const bool zero = (e | mhi | lo) == 0;
+    const bool normal = e - 897u <= 1150u - 897u;  // unbiased -126..127
+    const bool inf_or_quiet = e == 0x7FFu && ((mhi | lo) == 0 || (mhi & 0x80000u) != 0);
+    bad |= (lo & 0x1FFFFFFFu) | ((zero || normal || inf_or_quiet) ? 0ull : kNarrowFlag);
+    const unsigned int e32 = zero ? 0u : (e == 0x7FFu ? 0xFFu : ((e - 896u) & 0xFFu));
+    return (hi & 0x80000000u) | (e32 << 23) | (mhi << 3) | (lo >> 29);
+}
+
+__device__ __forceinline__ void narrow_test_i64(u32x4 v, unsigned long long& bad) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const long long x = (long long)(((unsigned long long)v[2 * j + 1] << 32) | v[2 * j]);
+        bad |= (unsigned long long)(x ^ (x >> 63)) | ((unsigned long long)x & kNarrowFlag);
+    }
+}
+
+__device__ __forceinline__ void narrow_test_i32(u32x4 v, unsigned long long& bad) {
+    unsigned int mag = 0, sign = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int x = (int)v[j];
+        mag |= (unsigned int)(x ^ (x >> 31));
+        sign |= v[j];
+    }
+    bad |= mag | ((unsigned long long)(sign & 0x80000000u) << 32);
+}
+
+// R: source bytes per target byte; kUnroll: steps per trip; piece_t: what one
+// source vector becomes; apply(): that piece, and the vector's part of `bad`
+template <int SRC, int DST> struct Narrow;
+template <> struct Narrow<CSP_KIND_F32, CSP_KIND_BF16> {
+    static const int R = 2, kUnroll = 2;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ piece_t apply(u32x4 v, unsigned long long& bad) {
+        bad |= (v[0] | v[1] | v[2] | v[3]) & 0xFFFFu;
+        return u32x2{(v[0] >> 16) | (v[1] & 0xFFFF0000u), (v[2] >> 16) | (v[3] & 0xFFFF0000u)};
+    }
+};
+template <> struct Narrow<CSP_KIND_F64, CSP_KIND_F32> {
+    static const int R = 2, kUnroll = 2;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ piece_t apply(u32x4 v, unsigned long long& bad) {
+        const unsigned int a = narrow_f64(v[0], v[1], bad);
+        const unsigned int b = narrow_f64(v[2], v[3], bad);
+        return u32x2{a, b};
+    }
+};
+template <> struct Narrow<CSP_KIND_I64, CSP_KIND_I32> {
+    static const int R = 2, kUnroll = 2;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ piece_t apply(u32x4 v, unsigned long long& bad) {
+        narrow_test_i64(v, bad);
+        return u32x2{v[0], v[2]};
+    }
+};
+template <> struct Narrow<CSP_KIND_I64, CSP_KIND_I16> {
+    static const int R = 4, kUnroll = 1;
+    typedef unsigned int piece_t;
+    static __device__ __forceinline__ piece_t apply(u32x4 v, unsigned long long& bad) {
+        narrow_test_i64(v, bad);
+        return (v[0] & 0xFFFFu) | (v[2] << 16);
+    }
+};
+template <> struct Narrow<CSP_KIND_I64, CSP_KIND_U8> {
+    static const int R = 8, kUnroll = 1;
+    typedef unsigned short piece_t;
+    static __device__ __forceinline__ piece_t apply(u32x4 v, unsigned long long& bad) {
+        narrow_test_i64(v, bad);
+        return (unsigned short)((v[0] & 0xFFu) | ((v[2] & 0xFFu) << 8));
+    }
+};
+template <> struct Narrow<CSP_KIND_I32, CSP_KIND_I16> {
+    static const int R = 2, kUnroll = 2;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ piece_t apply(u32x4 v, unsigned long long& bad) {
+        narrow_test_i32(v, bad);
+        return u32x2{(v[0] & 0xFFFFu) | (v[1] << 16), (v[2] & 0xFFFFu) | (v[3] << 16)};
+    }
+};
+template <> struct Narrow<CSP_KIND_I32, CSP_KIND_U8> {
+    static const int R = 4, kUnroll = 1;
+    typedef unsigned int piece_t;
+    static __device__ __forceinline__ piece_t apply(u32x4 v, unsigned long long& bad) {
+        narrow_test_i32(v, bad);
+        return (v[0] & 0xFFu) | ((v[1] & 0xFFu) << 8) | ((v[2] & 0xFFu) << 16) | (v[3] << 24);
+    }
+};
+
+static const int kNarrowStepVecs = 64;      // output vectors of one wave step
+static const int kNarrowStepsPerWave = 4;   // 4 waves x 4 steps x 1 KiB = one tile
+static_assert(4 * kNarrowStepsPerWave * kNarrowStepVecs == (int)kPackTileVecs,
+              "the pack kernel's tile");
+
+// the `rem` (1..3) whole 4-byte words that are left of the source's last,
+// partial vector: elements of 4 bytes one by one, one of 8 as its two words
+__device__ __forceinline__ u32x4 narrow_load_tail(const u32x4* p, unsigned int rem) {
+    const unsigned int* w = reinterpret_cast<const unsigned int*>(p);
+    u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (unsigned int j = 0; j < 3; ++j)
+        if (j < rem) v[j] = w[j];
+    return v;
+}
+
+// orders a wave's LDS writes before its LDS reads (and the reverse) for the
+// compiler; the hardware completes one wave's LDS operations in order
+__device__ __forceinline__ void narrow_strip_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// nsv: source vectors wholly below numel; rem: 4-byte words of the partial
+// one after them; nov: output vectors, the zero-padded last one included
+template <int SRC, int DST>
+__global__ __launch_bounds__(256) void csp_narrow_checksum_kernel(
+    const u32x4* __restrict__ src, size_t nsv, unsigned int rem, u32x4* __restrict__ dst,
+    size_t nov, size_t ntiles, unsigned long long* __restrict__ out) {
+    typedef Narrow<SRC, DST> N;
+    constexpr int R = N::R, U = N::kUnroll;
+    typedef typename N::piece_t piece_t;
+    static_assert(sizeof(piece_t) * R == 16, "R pieces make one output vector");
+    static_assert(kNarrowStepsPerWave % U == 0, "whole trips");
+    __shared__ u32x4 strip[4][U][kNarrowStepVecs];
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = threadIdx.x >> 6;
+    unsigned long long s0 = 0, t = 0, bad = 0;
+    for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        // step0 depends on the tile, the wave and j alone: every branch on it
+        // is wave-uniform, and all 64 lanes reach the strip together
+        for (int j = 0; j < kNarrowStepsPerWave; j += U) {
+            const size_t step0 = (tile * 4 + wave) * kNarrowStepsPerWave + j;
+            if (step0 * kNarrowStepVecs >= nov) break;  // the last tile's unused steps
+            const size_t sv0 = step0 * kNarrowStepVecs * R + lane;
+            u32x4 v[U * R];
+            if ((step0 + U) * kNarrowStepVecs * R <= nsv) {
+#pragma unroll
+                for (int i = 0; i < U * R; ++i)
+                    v[i] = __builtin_nontemporal_load(&src[sv0 + i * kNarrowStepVecs]);
+            } else {  // the trip that holds the source's end
+#pragma unroll
+                for (int i = 0; i < U * R; ++i) {
+                    const size_t sv = sv0 + i * kNarrowStepVecs;
+                    v[i] = u32x4{0u, 0u, 0u, 0u};
+                    if (sv < nsv) v[i] = __builtin_nontemporal_load(&src[sv]);
+                    else if (sv == nsv && rem != 0) v[i] = narrow_load_tail(src + nsv, rem);
+                }
+            }
+            if (dst == nullptr) {  // probe: uniform for the whole grid
+#pragma unroll
+                for (int i = 0; i < U * R; ++i) (void)N::apply(v[i], bad);
+                continue;
+            }
+#pragma unroll
+            for (int i = 0; i < U * R; ++i)
+                reinterpret_cast<piece_t*>(&strip[wave][i / R][0])[(i % R) * kNarrowStepVecs +
+                                                                    lane] = N::apply(v[i], bad);
+            narrow_strip_sync();
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const size_t ov = (step0 + u) * kNarrowStepVecs + lane;
+                const u32x4 o = strip[wave][u][lane];
+                if (ov < nov) {
+                    __builtin_nontemporal_store(o, &dst[ov]);
+                    checksum_add(s0, t, o, (unsigned int)(ov * 4));
+                }
+            }
+            narrow_strip_sync();  // the next trip overwrites the strip
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+        bad |= __shfl_down(bad, off, 64);
+    }
+    __shared__ unsigned long long part[3][4];
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+        part[2][wave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (dst != nullptr) {
+            atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+            atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+        }
+        atomicOr(&out[2], part[2][0] | part[2][1] | part[2][2] | part[2][3]);
+    }
+}
+
+typedef void (*narrow_fn)(const u32x4*, size_t, unsigned int, u32x4*, size_t, size_t,
+                          unsigned long long*);
+
+struct NarrowPairInfo {
+    int src_kind, dst_kind;
+    unsigned int src_es, dst_es;
+    narrow_fn fn;
+};
+
+#define CSP_NARROW_PAIR(S, SES, D, DES) \
+    {CSP_KIND_##S, CSP_KIND_##D, SES, DES, csp_narrow_checksum_kernel<CSP_KIND_##S, CSP_KIND_##D>}
+static const NarrowPairInfo kNarrowPairs[] = {
+    CSP_NARROW_PAIR(F32, 4, BF16, 2), CSP_NARROW_PAIR(F64, 8, F32, 4),
+    CSP_NARROW_PAIR(I64, 8, I32, 4),  CSP_NARROW_PAIR(I64, 8, I16, 2),
+    CSP_NARROW_PAIR(I64, 8, U8, 1),   CSP_NARROW_PAIR(I32, 4, I16, 2),
+    CSP_NARROW_PAIR(I32, 4, U8, 1),
+};
+#undef CSP_NARROW_PAIR
+
+// the bit of every target of src_kind that `bad` leaves exact
+static uint32_t narrow_fits(int src_kind, unsigned long long bad) {
+    const unsigned long long mag = bad & ~kNarrowFlag;
+    const bool neg = (bad & kNarrowFlag) != 0;
+    uint32_t fits = 0;
+    if (src_kind == CSP_KIND_F32 && bad == 0) fits |= 1u << CSP_KIND_BF16;
+    if (src_kind == CSP_KIND_F64 && bad == 0) fits |= 1u << CSP_KIND_F32;
+    if (src_kind == CSP_KIND_I64 && mag < (1ull << 31)) fits |= 1u << CSP_KIND_I32;
+    if (src_kind == CSP_KIND_I64 || src_kind == CSP_KIND_I32) {
+        if (mag < (1ull << 15)) fits |= 1u << CSP_KIND_I16;
+        if (mag < (1ull << 8) && !neg) fits |= 1u << CSP_KIND_U8;
+    }
+    return fits;
+}
+
+static const size_t kNarrowGridCapDefault = 1024;
+static size_t g_narrow_grid_cap = kNarrowGridCapDefault;
+static const uint64_t kNarrowMaxSrcBytes = uint64_t(16) << 30;
+
+// Tools only: the grid cap of the next csp_narrow_checksum_dev calls (0
+// restores the default).  Returns the cap in effect.  With a cap of 1, 2 or 3
+// workgroups a few tiles make every workgroup take several trips.
+extern "C" size_t csp_narrow_checksum_grid_cap(size_t cap) {
+    g_narrow_grid_cap = cap ? std::min(cap, size_t(65536)) : kNarrowGridCapDefault;
+    return g_narrow_grid_cap;
+}
+
+// Test the numel contiguous elements of kind src_kind at device pointer src
+// for exact narrowing and put into *fits one bit, 1 << kind, per target of
+// src_kind that reproduces every element bit for bit when widened back.
+//
+//   - dst == nullptr: a probe.  Nothing is stored, dst_kind and dst_bytes
+//     are not looked at, sums is zero;
+//   - dst set: the elements narrowed to dst_kind are also written to dst,
+//     zero padded to dst_bytes = numel * (element size of dst_kind) rounded up
+//     to 16, whatever the verdict.  If the bit of dst_kind is set in *fits,
+//     sums equals csp_checksum_dev(dst, dst_bytes); if it is clear, dst and
+//     sums mean nothing.
+//
+// Kinds: 0 float32, 1 float64, 2 int32, 3 int64, 4 bfloat16, 5 int16,
+// 6 uint8; pairs: 0->4, 1->0, 3->2, 3->5, 3->6, 2->5, 2->6.  Returns 0, or -1
+// with a message and nothing launched for a null sums, fits or src, a pair
+// (a probe: a source) that is not served, a src or dst that is not 16-byte
+// aligned, a wrong dst_bytes, a source above 16 GiB or a dst that overlaps
+// src; and for a HIP failure.  numel == 0 returns 0 with every bit of
+// src_kind's targets set and zero sums.  Runs on copy_stream() and
+// synchronises it before returning; a src written on another stream must be
+// complete first.  kernel_ms (optional): the kernel alone, from events around
+// the launch.
+extern "C" int csp_narrow_checksum_dev(const void* src, size_t numel, int src_kind,
+                                       int dst_kind, void* dst, size_t dst_bytes,
+                                       uint64_t sums[2], uint32_t* fits, float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (sums == nullptr || fits == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_narrow_checksum_dev: null output pointer");
+        return -1;
+    }
+    sums[0] = sums[1] = 0;
+    *fits = 0;
+    const NarrowPairInfo* pair = nullptr;
+    for (const NarrowPairInfo& p : kNarrowPairs)
+        if (p.src_kind == src_kind && (dst == nullptr || p.dst_kind == dst_kind)) {
+            pair = &p;
+            break;
+        }
+    if (pair == nullptr) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_narrow_checksum_dev: no narrowing from kind %d to kind %d", src_kind,
+                 dst == nullptr ? -1 : dst_kind);
+        return -1;
+    }
+    if (numel == 0) {
+        *fits = narrow_fits(src_kind, 0);
+        return 0;
+    }
+    const uintptr_t s_addr = reinterpret_cast<uintptr_t>(src);
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dst);
+    if (s_addr == 0) {
+        snprintf(g_err, sizeof(g_err), "csp_narrow_checksum_dev: null src for %zu elements",
+                 numel);
+        return -1;
+    }
+    if (s_addr % 16 != 0 || d % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_narrow_checksum_dev: src %p and dst %p must be 16-byte aligned", src, dst);
+        return -1;
+    }
+    if (numel > kNarrowMaxSrcBytes / pair->src_es) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_narrow_checksum_dev: %zu elements of %u bytes are above the 16 GiB bound",
+                 numel, pair->src_es);
+        return -1;
+    }
+    const size_t src_bytes = numel * pair->src_es;
+    const size_t want = (numel * pair->dst_es + 15) / 16 * 16;
+    if (dst != nullptr) {
+        if (dst_bytes != want) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_narrow_checksum_dev: dst_bytes %zu, %zu elements of %u bytes need %zu",
+                     dst_bytes, numel, pair->dst_es, want);
+            return -1;
+        }
+        if (s_addr + src_bytes < s_addr || d + want < d ||
+            (d < s_addr + src_bytes && s_addr < d + want)) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_narrow_checksum_dev: %zu bytes at dst %p overlap %zu bytes at src %p",
+                     want, dst, src_bytes, src);
+            return -1;
+        }
+    }
+
+    // two sums and the `bad` word per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static int acc_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (acc == nullptr || acc_device != device) {
+        if (acc) (void)hipFree(acc);
+        acc = nullptr;
+        HIP_TRY(hipMalloc(&acc, 3 * sizeof(unsigned long long)));
+        acc_device = device;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define NARROW_TRY(expr)                                           \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    NARROW_TRY(hipMemsetAsync(acc, 0, 3 * sizeof(unsigned long long), s));
+    const size_t nsv = src_bytes / 16;
+    const unsigned int rem = (unsigned int)(src_bytes % 16 / 4);
+    const size_t nov = want / 16;
+    const size_t ntiles = (nov + kPackTileVecs - 1) / kPackTileVecs;
+    const size_t blocks = std::min(ntiles, g_narrow_grid_cap);
+    if (t0) NARROW_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(pair->fn, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       static_cast<const u32x4*>(src), nsv, rem, static_cast<u32x4*>(dst), nov,
+                       ntiles, acc);
+    NARROW_TRY(hipGetLastError());
+    if (t1) NARROW_TRY(hipEventRecord(t1, s));
+    unsigned long long host[3] = {0, 0, 0};
+    NARROW_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    NARROW_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) NARROW_TRY(hipEventElapsedTime(kernel_ms, t0, t1));
+#undef NARROW_TRY
+    sums[0] = host[0];
+    sums[1] = host[1];
+    *fits = narrow_fits(src_kind, host[2]);
+    return done(0);
+}
+
 // On-box variant exploration for the HBM sweep (tools only; the probe
 // uses g_sweep_variant).  Returns measured GB/s via *gbps.
 extern "C" int csp_hbm_bench(int device, int variant, size_t bytes, int reps,

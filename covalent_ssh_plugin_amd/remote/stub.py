@@ -74,6 +74,7 @@ def render_worker(
     retain_min_bytes: Optional[int] = None,
     delta_max_fraction: Optional[float] = None,
     gather_results: bool = False,
+    narrow_results: bool = False,
 ) -> str:
     """Return the persistent worker script text (one per endpoint; the
     GPU slot arrives via the CSP_GPU_SLOT env var at launch).  With
@@ -92,7 +93,10 @@ def render_worker(
     most that share of the blocks differs from the cached argument of the
     same size leaves as a block delta.  ``gather_results``
     (``gather_tensor_results``) makes the worker lay out large non-contiguous
-    CUDA results with csp_gather_checksum_dev in place of ``contiguous()``."""
+    CUDA results with csp_gather_checksum_dev in place of ``contiguous()``.
+    ``narrow_results`` (``narrow_tensor_results``) makes it send large
+    contiguous float32, float64, int32 and int64 CUDA results at the narrowest
+    width csp_narrow_checksum_dev finds exact."""
     text = _template_text(str(_WORKER_TEMPLATE_PATH))
     thr = DEFAULT_STAGING_THRESHOLD if staging_threshold is None else int(staging_threshold)
     replacements = {
@@ -112,6 +116,7 @@ def render_worker(
             -1.0 if delta_max_fraction is None else float(delta_max_fraction)
         ),
         "__CSP_GATHER_RESULTS__": repr(bool(gather_results)),
+        "__CSP_NARROW_RESULTS__": repr(bool(narrow_results)),
     }
     for token, value in replacements.items():
         text = text.replace(token, value)

@@ -116,7 +116,18 @@ Protocol (all frames: 8-byte big-endian length + payload):
              contiguous(); the frames and their meta are the same bytes
              either way, meta["staging"] counts "gathered_tensors" and
              "gathered_bytes", and a tensor the kernel refuses takes
-             contiguous() with the reason in "gather_fallback".  The packed
+             contiguous() with the reason in "gather_fallback".  With the
+             executor option narrow_tensor_results a large contiguous
+             float32, float64, int32 or int64 CUDA tensor that is neither
+             packed nor retained is tested by ONE csp_narrow_checksum_dev
+             call (integers: a probe first) and, when every element comes
+             back bit for bit from a narrower type, leaves as that type's
+             bytes: meta["buffers"][i] keeps "dtype" and "shape" and gains
+             "wire": the narrow dtype, and "sum" over the narrow bytes;
+             meta["staging"] counts "narrowed", "narrow_saved_bytes" and
+             "narrow_ms" (the calls and the buffer, the inexact ones too),
+             and a tensor that is not exact or is refused travels whole
+             with the reason in "narrow_fallback".  The packed
              arena likewise: its non-contiguous tensors that
              csp_gather_supported serves stay as they are and ONE
              csp_pack_gather_checksum_dev call fills and sums the arena from
@@ -165,6 +176,19 @@ DELTA_BLOCK = 4096  # csp_diff_block_bytes()
 # Lay out a large non-contiguous CUDA result with csp_gather_checksum_dev in
 # place of torch's contiguous() (executor option gather_tensor_results).
 GATHER_RESULTS = bool(__CSP_GATHER_RESULTS__)
+# Send a large contiguous float32, float64, int32 or int64 CUDA result at the
+# narrowest width that gives every element back bit for bit, tested, narrowed
+# and summed by csp_narrow_checksum_dev (executor option narrow_tensor_results).
+NARROW_RESULTS = bool(__CSP_NARROW_RESULTS__)
+# csp_narrow_checksum_dev's kinds and, per source, (target, kind, element
+# size) from the narrowest to the widest
+NARROW_KINDS = {"float32": 0, "float64": 1, "int32": 2, "int64": 3}
+NARROW_TARGETS = {
+    "float32": (("bfloat16", 4, 2),),
+    "float64": (("float32", 0, 4),),
+    "int64": (("uint8", 6, 1), ("int16", 5, 2), ("int32", 2, 4)),
+    "int32": (("uint8", 6, 1), ("int16", 5, 2)),
+}
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
 # break the children) and every electron executes in a freshly forked
@@ -355,6 +379,19 @@ def _load_gpu_lib():
             ctypes.POINTER(ctypes.c_uint64),
             ctypes.POINTER(ctypes.c_double),
             ctypes.POINTER(ctypes.c_int),
+        ]
+    if NARROW_RESULTS and hasattr(lib, "csp_narrow_checksum_dev"):
+        lib.csp_narrow_checksum_dev.restype = ctypes.c_int
+        lib.csp_narrow_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_int,
+            ctypes.c_int,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint32),
+            ctypes.POINTER(ctypes.c_float),
         ]
     if GATHER_RESULTS and hasattr(lib, "csp_pack_gather_checksum_dev"):
         lib.csp_pack_gather_checksum_dev.restype = ctypes.c_int
@@ -553,6 +590,63 @@ def _gather_into(lib, t, dst_ptr, total, stats):
     stats["gathered_tensors"] = stats.get("gathered_tensors", 0) + 1
     stats["gathered_bytes"] = stats.get("gathered_bytes", 0) + t.numel() * t.element_size()
     return [int(out[0]), int(out[1])]
+
+
+def _narrow(lib, t, stats):
+    """The contiguous CUDA tensor ``t`` at the narrowest width that is exact:
+    (uint8 device buffer, its bytes, the target's dtype name, [s0, s1] of
+    those bytes), or None with the reason in stats["narrow_fallback"]: a
+    narrowing never fails a task.  A float takes ONE csp_narrow_checksum_dev
+    call straight into the buffer; an integer a probe (no buffer, no stores)
+    and then one call at the tightest target the probe found.  The caller has
+    synchronised the null stream."""
+    import ctypes
+
+    import torch
+
+    def call(dst_kind, dst_ptr, dst_bytes):
+        sums = (ctypes.c_uint64 * 2)()
+        fits = ctypes.c_uint32()
+        rc = lib.csp_narrow_checksum_dev(
+            ctypes.c_void_p(t.data_ptr()), t.numel(), NARROW_KINDS[src], dst_kind,
+            ctypes.c_void_p(dst_ptr or None), dst_bytes, sums, ctypes.byref(fits), None,
+        )
+        if rc != 0:
+            raise RuntimeError(
+                "csp_narrow_checksum_dev failed (rc=%d): %s"
+                % (rc, lib.csp_last_error().decode(errors="replace"))
+            )
+        return fits.value, [int(sums[0]), int(sums[1])]
+
+    src = str(t.dtype).replace("torch.", "")
+    t0 = time.monotonic()
+    try:
+        if not hasattr(lib, "csp_narrow_checksum_dev"):
+            raise RuntimeError("the GPU library has no csp_narrow_checksum_dev")
+        targets = NARROW_TARGETS[src]
+        if len(targets) > 1:
+            fits, _ = call(-1, 0, 0)
+            targets = [x for x in targets if fits >> x[1] & 1][:1]
+            if not targets:
+                raise ValueError("no narrower %s target holds every element" % src)
+        name, kind, size = targets[0]
+        wire = t.numel() * size
+        total = (wire + 15) // 16 * 16
+        flat = torch.empty(total, dtype=torch.uint8, device="cuda")
+        fits, sums = call(kind, flat.data_ptr(), total)
+        if not fits >> kind & 1:
+            raise ValueError("%s elements are not exact as %s" % (src, name))
+    except Exception as e:  # noqa: BLE001
+        stats["narrow_fallback"] = repr(e)[:500]
+        return None
+    finally:
+        stats["narrow_ms"] = round(
+            stats.get("narrow_ms", 0.0) + (time.monotonic() - t0) * 1000, 3)
+    stats["narrowed"] = stats.get("narrowed", 0) + 1
+    stats["narrow_saved_bytes"] = (
+        stats.get("narrow_saved_bytes", 0) + t.numel() * t.element_size() - wire
+    )
+    return flat, wire, name, sums
 
 
 def _packs_strided(lib, t):
@@ -960,6 +1054,23 @@ def _stage_result(result, stats, buffers, buffer_meta, retain=None):
                 src_t = t.contiguous()
             # the library's copy stream does not wait on the null stream
             torch.cuda.synchronize()
+            if (
+                NARROW_RESULTS
+                and src_t is t
+                and str(t.dtype).replace("torch.", "") in NARROW_TARGETS
+                and t.data_ptr() % 16 == 0
+            ):
+                narrowed = _narrow(lib, t, stats)
+                if narrowed is not None:
+                    flat, wire, name, sums = narrowed
+                    stats["pinned_tensors"] += 1
+                    stats["mode"] = "pinned"
+                    marker = emit_buffer(
+                        _DeferredCuda(lib, flat.data_ptr(), wire), flat, t.dtype, t.shape
+                    )
+                    buffer_meta[-1]["wire"] = name
+                    buffer_meta[-1]["sum"] = sums
+                    return marker
             view = _DeferredCuda(lib, src_t.data_ptr(), nbytes)
             stats["pinned_tensors"] += 1
             stats["mode"] = "pinned"
@@ -1015,6 +1126,8 @@ def _delta_results(lib, masters, buffers, buffer_meta, stats):
     for i, (view, _keep) in enumerate(buffers):
         if not isinstance(view, _DeferredCuda) or view.nbytes < floor:
             continue
+        if "wire" in buffer_meta[i]:
+            continue  # narrowed: these are not the result's own bytes
         pair = next(
             (k for k, m in enumerate(masters) if k not in used and m[2] == view.nbytes),
             None,

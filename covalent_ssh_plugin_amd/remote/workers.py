@@ -526,8 +526,9 @@ def verify_result_buffers(buffer_meta, buffers) -> int:
         # looked up at call time: None when libcsp_io.so is not loaded.  A
         # retained buffer may be a whole large tensor: the same two numbers,
         # from pieces summed on the thread pool; so may one rebuilt from a
-        # delta (delta_tensor_results)
-        if "retained" in info or "delta" in info:
+        # delta (delta_tensor_results) or one that arrived narrowed
+        # (narrow_tensor_results), whose sum is over the narrow bytes
+        if "retained" in info or "delta" in info or "wire" in info:
             sums = threaded_checksum(buffers[i])
         else:
             sums = native_io.checksum(buffers[i])
@@ -603,6 +604,20 @@ def apply_result_delta(info, frame, base_view) -> bytearray:
     return out
 
 
+def widen_result(data, info):
+    """The tensor of a result buffer that crossed the pipe narrowed
+    (``narrow_tensor_results``): ``data`` holds ``info["wire"]`` elements, and
+    the result is ``info["dtype"]`` of ``info["shape"]``.  The worker narrows
+    only what this widening gives back bit for bit: bfloat16 to float32 appends
+    16 zero bits, float32 to float64 is exact for the zeros, normals,
+    infinities and quiet NaNs it lets through, and integers are sign- or
+    zero-extended.  The result owns new memory."""
+    import torch
+
+    narrow = torch.frombuffer(data, dtype=getattr(torch, info["wire"]))
+    return narrow.reshape(info["shape"]).to(getattr(torch, info["dtype"]))
+
+
 def _reconstruct(result, buffer_meta, buffers, rebuilt_out=None):
     """Replace out-of-band tensor-buffer markers with rebuilt torch
     tensors (workers ship large tensors as raw frames; see
@@ -651,7 +666,10 @@ def _reconstruct(result, buffer_meta, buffers, rebuilt_out=None):
         # large frames arrive in a preallocated writable buffer (zero-copy
         # here); small ones as bytes (copy once into writable memory)
         data = bytearray(raw) if isinstance(raw, bytes) else raw
-        t = torch.frombuffer(data, dtype=dtype).reshape(info["shape"])
+        if "wire" in info:
+            t = widen_result(data, info)
+        else:
+            t = torch.frombuffer(data, dtype=dtype).reshape(info["shape"])
         if rebuilt_out is not None:
             rebuilt_out[i] = t
         return t

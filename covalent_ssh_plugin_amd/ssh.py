@@ -201,6 +201,15 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # costs a launch and an allocation per tensor.  The wire format does not
     # change.
     "gather_tensor_results": False,
+    # A large contiguous float32, float64, int32 or int64 CUDA result crosses
+    # the pipe at the narrowest width that loses nothing: float32 whose low 16
+    # bits are all zero (the output of a bf16 computation) as bfloat16,
+    # float64 that holds float32 values as float32, integers (token ids,
+    # labels, indices) as uint8, int16 or int32.  One kernel launch on the
+    # worker tests every element, narrows and checksums; the dispatcher
+    # verifies the narrow bytes and widens them back, bit for bit.  A tensor
+    # with one element that does not fit travels whole, as without the option.
+    "narrow_tensor_results": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -405,6 +414,7 @@ class SSHExecutor(RemoteExecutor):
         retain_tensor_results: Optional[bool] = None,
         delta_tensor_results: Optional[bool] = None,
         gather_tensor_results: Optional[bool] = None,
+        narrow_tensor_results: Optional[bool] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -559,6 +569,14 @@ class SSHExecutor(RemoteExecutor):
         self.gather_tensor_results = bool(
             _conf("gather_tensor_results", gather_tensor_results, default=False)
         )
+        self.narrow_tensor_results = bool(
+            _conf("narrow_tensor_results", narrow_tensor_results, default=False)
+        )
+        if self.narrow_tensor_results and not self.persistent_workers:
+            raise ValueError(
+                "narrow_tensor_results needs persistent_workers or isolate_tasks: "
+                "only the worker channel carries result tensors out of band"
+            )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -1056,6 +1074,7 @@ class SSHExecutor(RemoteExecutor):
                 self.patch_args_max_fraction if self.delta_tensor_results else None
             ),
             gather_results=self.gather_tensor_results,
+            narrow_results=self.narrow_tensor_results,
         )
         digest = _script_digest(text)
         key = self._pool_key()
