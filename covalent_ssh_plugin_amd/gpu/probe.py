@@ -35,6 +35,9 @@ gfx950 only) provides:
 * ``csp_narrow_checksum_dev`` — a contiguous float32, float64, int32 or int64
   device tensor tested for a lossless narrower form, written in that form and
   checksummed by one launch (``narrow_tensor_results``),
+* ``csp_widen_checksum_dev`` — the inverse for arguments: narrow bytes in HBM
+  widened into one or two destinations and checksummed by one launch
+  (``narrow_tensor_args``),
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
   ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
@@ -263,6 +266,19 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_narrow_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_narrow_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_widen_checksum_dev.restype = ctypes.c_int
+    lib.csp_widen_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_int,
+        ctypes.c_int,
+        ctypes.c_void_p,
+        ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_float),
+    ]
+    lib.csp_widen_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_widen_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_gather_checksum_dev.restype = ctypes.c_int
     lib.csp_gather_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -804,6 +820,38 @@ def narrow_checksum_grid_cap(cap: int = 0) -> int:
     """Tools only: set the grid cap of :func:`narrow_checksum_device` (0
     restores the shipped default).  Returns the cap in effect."""
     return int(load().csp_narrow_checksum_grid_cap(int(cap)))
+
+
+def widen_checksum_device(
+    src_ptr: int, numel: int, narrow: str, wide: str, dst_ptr: int, dst2_ptr: int = 0
+) -> dict:
+    """Widen the ``numel`` contiguous ``narrow`` elements at device pointer
+    ``src_ptr`` to ``wide`` (a pair of ``NARROW_TARGETS`` read backwards;
+    ``narrow_tensor_args``) into ``dst_ptr`` and, when set, ``dst2_ptr`` as
+    well, in one kernel launch.  Returns ``{"rc", "sum", "kernel_ms"}``;
+    ``sum`` equals ``checksum_device(dst_ptr, numel * NARROW_ELEM_SIZE[wide])``.
+    The source must be readable up to ``narrow_bytes(numel, narrow)``, its pad
+    bytes may hold anything; the destinations are exactly the wide bytes.  An
+    unserved pair, a null or misaligned pointer, wide bytes above 16 GiB or
+    overlapping buffers raise ``GpuLibError`` and launch nothing.  Runs on the
+    library's copy stream; a source written on another stream must be complete
+    first."""
+    lib = load()
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_float()
+    rc = lib.csp_widen_checksum_dev(
+        ctypes.c_void_p(src_ptr or None), numel, NARROW_KINDS.get(narrow, -1),
+        NARROW_KINDS.get(wide, -1), ctypes.c_void_p(dst_ptr or None),
+        ctypes.c_void_p(dst2_ptr or None), out, ctypes.byref(kernel_ms),
+    )
+    _check(lib, rc, "csp_widen_checksum_dev")
+    return {"rc": rc, "sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
+
+
+def widen_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`widen_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_widen_checksum_grid_cap(int(cap)))
 
 
 GATHER_PATHS = {0: "none", 1: "direct", 2: "direct16", 3: "transpose", 5: "slab"}

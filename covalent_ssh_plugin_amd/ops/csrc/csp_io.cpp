@@ -11,6 +11,9 @@
 //                      pages, as the destination of a large frame
 //   csp_io_checksum    the two-word argument checksum (definition in
 //                      csp_io.h), computed where the tensor leaves
+//   csp_io_narrow      one pass over a chunk of a tensor argument: tests it
+//                      for lossless narrowing and writes the narrow elements
+//                      (narrow_tensor_args; the worker widens on the GPU)
 //
 // Return codes: see csp_io.h.
 
@@ -52,6 +55,12 @@ __attribute__((target_clones("avx2", "default")))
 #endif
 void csp_io_checksum(const void* src, size_t n, uint64_t out[2]) {
     csp_io_detail::checksum(src, n, out);
+}
+
+// One chunk of an argument narrowed for the wire (definition in csp_io.h).
+int csp_io_narrow(const void* src, size_t numel, int src_kind, int dst_kind, void* dst,
+                  uint64_t* bad) {
+    return csp_io_detail::narrow(src, numel, src_kind, dst_kind, dst, bad);
 }
 
 }  // extern "C"

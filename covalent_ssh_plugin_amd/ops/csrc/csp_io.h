@@ -162,4 +162,94 @@ static inline void checksum(const void* src, size_t n, uint64_t out[2]) {
     out[1] = s1 + s0;
 }
 
+// The host half of lossless narrowing (narrow_tensor_args): what
+// csp_narrow_checksum_kernel in csp_gpu.hip does to a result on the GPU, done
+// to an argument where it leaves.  Exactness is decided on the bits by the
+// rules of the block comment above that kernel, the CPU's float conversion
+// takes no part, and `bad` has that kernel's meaning: for floats the bits
+// that had to be zero (bit 63: wrong class of value), for integers the OR of
+// x ^ (x >> sign) and in bit 63 the OR of the signs.  csp_widen_checksum_kernel
+// gives back exactly what a clean `bad` let through.
+static const uint64_t kNarrowFlag = uint64_t(1) << 63;
+enum { kKindF32 = 0, kKindF64 = 1, kKindI32 = 2, kKindI64 = 3, kKindBF16 = 4, kKindI16 = 5,
+       kKindU8 = 6 };
+
+static inline uint16_t narrow_f32(uint32_t x, uint64_t& bad) {
+    bad |= x & 0xFFFFu;
+    return uint16_t(x >> 16);
+}
+
+static inline uint32_t narrow_f64(uint64_t x, uint64_t& bad) {
+    const uint32_t lo = uint32_t(x), hi = uint32_t(x >> 32);
+    const uint32_t e = (hi >> 20) & 0x7FFu;
+    const uint32_t mhi = hi & 0xFFFFFu;  // the top 20 mantissa bits
+    const bool zero = (e | mhi | lo) == 0;
+    const bool normal = e - 897u <= 1150u - 897u;  // unbiased -126..127
+    const bool inf_or_quiet = e == 0x7FFu && ((mhi | lo) == 0 || (mhi & 0x80000u) != 0);
+    bad |= (lo & 0x1FFFFFFFu) | ((zero || normal || inf_or_quiet) ? uint64_t(0) : kNarrowFlag);
+    const uint32_t e32 = zero ? 0u : (e == 0x7FFu ? 0xFFu : ((e - 896u) & 0xFFu));
+    return (hi & 0x80000000u) | (e32 << 23) | (mhi << 3) | (lo >> 29);
+}
+
+template <typename D> static inline D narrow_i64(uint64_t x, uint64_t& bad) {
+    const int64_t s = int64_t(x);
+    bad |= uint64_t(s ^ (s >> 63)) | (x & kNarrowFlag);
+    return D(x);  // the low bytes
+}
+
+template <typename D> static inline D narrow_i32(uint32_t x, uint64_t& bad) {
+    const int32_t s = int32_t(x);
+    bad |= uint32_t(s ^ (s >> 31)) | (uint64_t(x & 0x80000000u) << 32);
+    return D(x);
+}
+
+// numel elements of S at src through f; the narrow ones to dst when it is set
+template <typename S, typename D, D (*F)(S, uint64_t&)>
+static inline void narrow_loop(const void* src, size_t numel, void* dst, uint64_t* bad) {
+    const unsigned char* p = static_cast<const unsigned char*>(src);
+    unsigned char* q = static_cast<unsigned char*>(dst);
+    uint64_t b = 0;
+    for (size_t i = 0; i < numel; ++i) {
+        S x;
+        memcpy(&x, p + i * sizeof(S), sizeof(S));  // unaligned-safe; little-endian hosts only
+        const D y = F(x, b);
+        if (q) memcpy(q + i * sizeof(D), &y, sizeof(D));
+    }
+    *bad |= b;
+}
+
+// One pass over numel elements of src_kind: ORs into *bad what speaks against
+// narrowing them exactly and, when dst is set, writes them narrowed to
+// dst_kind (numel * its element size bytes), whatever the verdict.  Kinds and
+// pairs are csp_narrow_checksum_dev's.  Returns 0, or -1 for a pair that is
+// not served or a null bad.
+static inline int narrow(const void* src, size_t numel, int src_kind, int dst_kind, void* dst,
+                         uint64_t* bad) {
+    if (bad == nullptr) return -1;
+    switch (src_kind * 8 + dst_kind) {
+    case kKindF32 * 8 + kKindBF16:
+        narrow_loop<uint32_t, uint16_t, narrow_f32>(src, numel, dst, bad);
+        return 0;
+    case kKindF64 * 8 + kKindF32:
+        narrow_loop<uint64_t, uint32_t, narrow_f64>(src, numel, dst, bad);
+        return 0;
+    case kKindI64 * 8 + kKindI32:
+        narrow_loop<uint64_t, uint32_t, narrow_i64<uint32_t>>(src, numel, dst, bad);
+        return 0;
+    case kKindI64 * 8 + kKindI16:
+        narrow_loop<uint64_t, uint16_t, narrow_i64<uint16_t>>(src, numel, dst, bad);
+        return 0;
+    case kKindI64 * 8 + kKindU8:
+        narrow_loop<uint64_t, uint8_t, narrow_i64<uint8_t>>(src, numel, dst, bad);
+        return 0;
+    case kKindI32 * 8 + kKindI16:
+        narrow_loop<uint32_t, uint16_t, narrow_i32<uint16_t>>(src, numel, dst, bad);
+        return 0;
+    case kKindI32 * 8 + kKindU8:
+        narrow_loop<uint32_t, uint8_t, narrow_i32<uint8_t>>(src, numel, dst, bad);
+        return 0;
+    }
+    return -1;
+}
+
 }  // namespace csp_io_detail

@@ -4719,6 +4719,389 @@ extern "C" int csp_narrow_checksum_dev(const void* src, size_t numel, int src_ki
     return done(0);
 }
 
+// ---------------------------------------------------------------------------
+// Widening with checksum: a narrowed argument brought back to its own width
+// ---------------------------------------------------------------------------
+//
+// The inverse of the kernel above, for arguments (narrow_tensor_args): the
+// narrow bytes that crossed the pipe lie in HBM, and ONE pass reads them,
+// writes the wide tensor, optionally writes a second copy of it (the cached
+// master and the electron's private tensor) and computes csp_checksum_dev of
+// the wide bytes, which is the sum the dispatcher announced for the tensor's
+// own bytes.  torch's .to() followed by csp_checksum_dev and, with the cache,
+// csp_copy_checksum_dev would take three passes and a full-size temporary.
+//
+// Widening is done on the bits, by integer rules; no conversion instruction
+// and no denormal mode takes part, and nothing is multiplied, so there is
+// no MFMA here:
+//
+//   - bf16 -> f32: bits << 16;
+//   - f32 -> f64: sign, exponent 0 -> 0, 255 -> 0x7FF, otherwise + 896,
+//     mantissa << 29: the inverse of narrow_f64 for +-0, normals, +-inf and
+//     quiet NaNs.  A float32 subnormal or signalling NaN can only come from a
+//     corrupted frame; it goes through the same shifts, and the sum then
+//     disagrees with the announced one;
+//   - integers: signed sources sign-extend, uint8 zero-extends.
+//
+// Data movement.  The NARROW input is cut like the pack kernel's output:
+// 16 KiB tiles, 256-thread workgroups looping tile += gridDim.x.  One narrow
+// vector becomes R = wide bytes / narrow bytes wide vectors.  A lane that
+// widened its own narrow vector in place would give every store instruction
+// a stride of 16 * R bytes across the wave; instead the pieces change lanes
+// through LDS before they are widened:
+//
+//   - a wave owns 4 steps of a tile; a step is 64 narrow vectors (1 KiB) that
+//     become 64 * R wide vectors.  Each lane loads narrow vector
+//     step * 64 + lane, nontemporal and coalesced; all loads of a trip are
+//     issued before the first use.  A trip is four steps for R = 2 and two
+//     for R = 4 and 8 (not measured against other trip sizes);
+//   - each lane writes its vector as one b128 into a wave-private 1 KiB LDS
+//     strip at lane * 16, then for k = 0..R-1 reads the 16 / R byte piece at
+//     (k * 64 + lane) * 16 / R: ds_read_b64, b32 or b16, consecutive across
+//     the lanes, so no bank conflicts;
+//   - the piece is widened in registers to one 16-byte vector, summed at its
+//     word index in the wide buffer and stored nontemporally at wide vector
+//     step * 64 * R + k * 64 + lane: every store instruction of a wave writes
+//     1 KiB contiguously.  With dst2 set (uniform for the grid) the same
+//     registers are stored there too.  Only lanes of one wave share a strip:
+//     a wave-scope fence, no workgroup barrier.
+//
+// Edges: the narrow buffer is readable up to a multiple of 16 bytes but its
+// pad bytes are not initialised: what they widen to lies at or past numel and
+// is neither stored nor summed.  The wide buffers are exactly numel * wide
+// element size bytes; a last partial wide vector is stored word by word and
+// summed with its missing words as zero, which is csp_checksum_dev of that
+// byte count.  The steps of the last tile past the input are skipped
+// wave-uniformly.  At most 1024 workgroups: the cap of the other
+// checksum-carrying kernels, carried over, not measured for this one.
+
+// one f32 as the (lo, hi) words of the f64 of the same value
+__device__ __forceinline__ void widen_f32(unsigned int x, unsigned int& lo, unsigned int& hi) {
+    const unsigned int e = (x >> 23) & 0xFFu;
+    const unsigned int m = x & 0x7FFFFFu;
+    const unsigned int e64 = e == 0u ? 0u : (e == 0xFFu ? 0x7FFu : e + 896u);
+    lo = m << 29;
+    hi = (x & 0x80000000u) | (e64 << 20) | (m >> 3);
+}
+
+__device__ __forceinline__ unsigned int widen_sign(unsigned int x) {
+    return (unsigned int)((int)x >> 31);
+}
+__device__ __forceinline__ unsigned int widen_lo16(unsigned int p) {
+    return (unsigned int)((int)(p << 16) >> 16);
+}
+__device__ __forceinline__ unsigned int widen_hi16(unsigned int p) {
+    return (unsigned int)((int)p >> 16);
+}
+
+// R: wide bytes per narrow byte; kUnroll: steps per trip; piece_t: the part of
+// a narrow vector that one wide vector is made of; apply(): that wide vector
+template <int NARROW, int WIDE> struct Widen;
+template <> struct Widen<CSP_KIND_BF16, CSP_KIND_F32> {
+    static const int R = 2, kUnroll = 4;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ u32x4 apply(piece_t p) {
+        return u32x4{p[0] << 16, p[0] & 0xFFFF0000u, p[1] << 16, p[1] & 0xFFFF0000u};
+    }
+};
+template <> struct Widen<CSP_KIND_F32, CSP_KIND_F64> {
+    static const int R = 2, kUnroll = 4;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ u32x4 apply(piece_t p) {
+        u32x4 o;
+        unsigned int lo, hi;
+        widen_f32(p[0], lo, hi);
+        o[0] = lo, o[1] = hi;
+        widen_f32(p[1], lo, hi);
+        o[2] = lo, o[3] = hi;
+        return o;
+    }
+};
+template <> struct Widen<CSP_KIND_I32, CSP_KIND_I64> {
+    static const int R = 2, kUnroll = 4;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ u32x4 apply(piece_t p) {
+        return u32x4{p[0], widen_sign(p[0]), p[1], widen_sign(p[1])};
+    }
+};
+template <> struct Widen<CSP_KIND_I16, CSP_KIND_I64> {
+    static const int R = 4, kUnroll = 2;
+    typedef unsigned int piece_t;
+    static __device__ __forceinline__ u32x4 apply(piece_t p) {
+        const unsigned int a = widen_lo16(p), b = widen_hi16(p);
+        return u32x4{a, widen_sign(a), b, widen_sign(b)};
+    }
+};
+template <> struct Widen<CSP_KIND_U8, CSP_KIND_I64> {
+    static const int R = 8, kUnroll = 2;
+    typedef unsigned short piece_t;
+    static __device__ __forceinline__ u32x4 apply(piece_t p) {
+        return u32x4{(unsigned int)p & 0xFFu, 0u, (unsigned int)p >> 8, 0u};
+    }
+};
+template <> struct Widen<CSP_KIND_I16, CSP_KIND_I32> {
+    static const int R = 2, kUnroll = 4;
+    typedef u32x2 piece_t;
+    static __device__ __forceinline__ u32x4 apply(piece_t p) {
+        return u32x4{widen_lo16(p[0]), widen_hi16(p[0]), widen_lo16(p[1]), widen_hi16(p[1])};
+    }
+};
+template <> struct Widen<CSP_KIND_U8, CSP_KIND_I32> {
+    static const int R = 4, kUnroll = 2;
+    typedef unsigned int piece_t;
+    static __device__ __forceinline__ u32x4 apply(piece_t p) {
+        return u32x4{p & 0xFFu, (p >> 8) & 0xFFu, (p >> 16) & 0xFFu, p >> 24};
+    }
+};
+
+// one wide vector to a destination: whole below nwv, its first `rem` words at
+// nwv, nothing after that
+__device__ __forceinline__ void widen_store(u32x4* __restrict__ dst, size_t wv, size_t nwv,
+                                            unsigned int rem, u32x4 o) {
+    if (wv < nwv) {
+        __builtin_nontemporal_store(o, &dst[wv]);
+    } else {
+        unsigned int* w = reinterpret_cast<unsigned int*>(dst + nwv);
+#pragma unroll
+        for (unsigned int j = 0; j < 3; ++j)
+            if (j < rem) w[j] = o[j];
+    }
+}
+
+// nnv: narrow vectors, the last one possibly with pad bytes; nwv: wide
+// vectors wholly below numel; rem: 4-byte words of the partial one after them
+template <int NARROW, int WIDE>
+__global__ __launch_bounds__(256) void csp_widen_checksum_kernel(
+    const u32x4* __restrict__ src, size_t nnv, u32x4* __restrict__ dst, u32x4* __restrict__ dst2,
+    size_t nwv, unsigned int rem, size_t ntiles, unsigned long long* __restrict__ out) {
+    typedef Widen<NARROW, WIDE> W;
+    constexpr int R = W::R, U = W::kUnroll;
+    typedef typename W::piece_t piece_t;
+    static_assert(sizeof(piece_t) * R == 16, "R pieces make one narrow vector");
+    static_assert(kNarrowStepsPerWave % U == 0, "whole trips");
+    __shared__ u32x4 strip[4][U][kNarrowStepVecs];
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = threadIdx.x >> 6;
+    unsigned long long s0 = 0, t = 0;
+    for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        // step0 depends on the tile, the wave and j alone: every branch on it
+        // is wave-uniform, and all 64 lanes reach the strip together
+        for (int j = 0; j < kNarrowStepsPerWave; j += U) {
+            const size_t step0 = (tile * 4 + wave) * kNarrowStepsPerWave + j;
+            if (step0 * kNarrowStepVecs >= nnv) break;  // the last tile's unused steps
+            const size_t nv0 = step0 * kNarrowStepVecs + lane;
+            u32x4 v[U];
+            if ((step0 + U) * kNarrowStepVecs <= nnv) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    v[u] = __builtin_nontemporal_load(&src[nv0 + u * kNarrowStepVecs]);
+            } else {  // the trip that holds the input's end
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const size_t nv = nv0 + u * kNarrowStepVecs;
+                    v[u] = u32x4{0u, 0u, 0u, 0u};
+                    if (nv < nnv) v[u] = __builtin_nontemporal_load(&src[nv]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) strip[wave][u][lane] = v[u];
+            narrow_strip_sync();
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const piece_t* pieces = reinterpret_cast<const piece_t*>(&strip[wave][u][0]);
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+                    const size_t wv = ((step0 + u) * R + k) * kNarrowStepVecs + lane;
+                    u32x4 o = W::apply(pieces[k * kNarrowStepVecs + lane]);
+                    if (wv > nwv || (wv == nwv && rem == 0)) continue;
+                    if (wv == nwv) {  // the partial vector: its missing words are zero
+#pragma unroll
+                        for (unsigned int q = 1; q < 4; ++q)
+                            if (q >= rem) o[q] = 0u;
+                    }
+                    checksum_add(s0, t, o, (unsigned int)(wv * 4));
+                    widen_store(dst, wv, nwv, rem, o);
+                    if (dst2 != nullptr) widen_store(dst2, wv, nwv, rem, o);
+                }
+            }
+            narrow_strip_sync();  // the next trip overwrites the strip
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+typedef void (*widen_fn)(const u32x4*, size_t, u32x4*, u32x4*, size_t, unsigned int, size_t,
+                         unsigned long long*);
+
+struct WidenPairInfo {
+    int narrow_kind, wide_kind;
+    unsigned int narrow_es, wide_es;
+    widen_fn fn;
+};
+
+#define CSP_WIDEN_PAIR(N, NES, W, WES) \
+    {CSP_KIND_##N, CSP_KIND_##W, NES, WES, csp_widen_checksum_kernel<CSP_KIND_##N, CSP_KIND_##W>}
+static const WidenPairInfo kWidenPairs[] = {
+    CSP_WIDEN_PAIR(BF16, 2, F32, 4), CSP_WIDEN_PAIR(F32, 4, F64, 8),
+    CSP_WIDEN_PAIR(I32, 4, I64, 8),  CSP_WIDEN_PAIR(I16, 2, I64, 8),
+    CSP_WIDEN_PAIR(U8, 1, I64, 8),   CSP_WIDEN_PAIR(I16, 2, I32, 4),
+    CSP_WIDEN_PAIR(U8, 1, I32, 4),
+};
+#undef CSP_WIDEN_PAIR
+
+static const size_t kWidenGridCapDefault = 1024;
+static size_t g_widen_grid_cap = kWidenGridCapDefault;
+static const uint64_t kWidenMaxWideBytes = uint64_t(16) << 30;
+
+// Tools only: the grid cap of the next csp_widen_checksum_dev calls (0
+// restores the default).  Returns the cap in effect.  With a cap of 1, 2 or 3
+// workgroups a few tiles make every workgroup take several trips.
+extern "C" size_t csp_widen_checksum_grid_cap(size_t cap) {
+    g_widen_grid_cap = cap ? std::min(cap, size_t(65536)) : kWidenGridCapDefault;
+    return g_widen_grid_cap;
+}
+
+// Widen the numel contiguous elements of kind narrow_kind at device pointer
+// src to wide_kind, write them to dst and, when dst2 is set, to dst2 as well,
+// and put csp_checksum_dev(dst, numel * wide element size) into sums, all in
+// one kernel launch.  src must be readable up to numel * narrow element size
+// rounded up to 16; the pad bytes may hold anything.  dst and dst2 are
+// numel * wide element size bytes, and nothing past that is written.
+//
+// Kinds as for csp_narrow_checksum_dev; pairs: 4->0, 0->1, 2->3, 5->3, 6->3,
+// 5->2, 6->2.  Returns 0, or -1 with a message and nothing launched for a null
+// sums, src or dst, a pair that is not served, a src, dst or dst2 that is not
+// 16-byte aligned, wide bytes above 16 GiB or any overlap among the three
+// ranges (src taken with its rounded extent); and for a HIP failure.
+// numel == 0 returns 0 with zero sums.  Runs on copy_stream(), so it is
+// ordered after the copies that csp_h2d_stream_fd issued, and synchronises
+// that stream before returning.  kernel_ms (optional): the kernel alone, from
+// events around the launch.
+extern "C" int csp_widen_checksum_dev(const void* src, size_t numel, int narrow_kind,
+                                      int wide_kind, void* dst, void* dst2, uint64_t sums[2],
+                                      float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (sums == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_widen_checksum_dev: null output pointer");
+        return -1;
+    }
+    sums[0] = sums[1] = 0;
+    const WidenPairInfo* pair = nullptr;
+    for (const WidenPairInfo& p : kWidenPairs)
+        if (p.narrow_kind == narrow_kind && p.wide_kind == wide_kind) {
+            pair = &p;
+            break;
+        }
+    if (pair == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_widen_checksum_dev: no widening from kind %d to kind %d",
+                 narrow_kind, wide_kind);
+        return -1;
+    }
+    if (numel == 0) return 0;
+    const uintptr_t s_addr = reinterpret_cast<uintptr_t>(src);
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t d2 = reinterpret_cast<uintptr_t>(dst2);
+    if (s_addr == 0 || d == 0) {
+        snprintf(g_err, sizeof(g_err), "csp_widen_checksum_dev: null src or dst for %zu elements",
+                 numel);
+        return -1;
+    }
+    if (s_addr % 16 != 0 || d % 16 != 0 || d2 % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_widen_checksum_dev: src %p, dst %p and dst2 %p must be 16-byte aligned", src,
+                 dst, dst2);
+        return -1;
+    }
+    if (numel > kWidenMaxWideBytes / pair->wide_es) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_widen_checksum_dev: %zu elements of %u bytes are above the 16 GiB bound",
+                 numel, pair->wide_es);
+        return -1;
+    }
+    const size_t wide_bytes = numel * pair->wide_es;
+    const size_t narrow_bytes = (numel * pair->narrow_es + 15) / 16 * 16;
+    auto overlap = [](uintptr_t a, size_t na, uintptr_t b, size_t nb) {
+        return a + na < a || b + nb < b || (a < b + nb && b < a + na);
+    };
+    if (overlap(s_addr, narrow_bytes, d, wide_bytes) ||
+        (d2 != 0 && (overlap(s_addr, narrow_bytes, d2, wide_bytes) ||
+                     overlap(d, wide_bytes, d2, wide_bytes)))) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_widen_checksum_dev: %zu bytes at src %p, %zu bytes at dst %p and at dst2 %p "
+                 "overlap",
+                 narrow_bytes, src, wide_bytes, dst, dst2);
+        return -1;
+    }
+
+    // one accumulator pair per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static int acc_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (acc == nullptr || acc_device != device) {
+        if (acc) (void)hipFree(acc);
+        acc = nullptr;
+        HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+        acc_device = device;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define WIDEN_TRY(expr)                                            \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    WIDEN_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t nnv = narrow_bytes / 16;
+    const size_t nwv = wide_bytes / 16;
+    const unsigned int rem = (unsigned int)(wide_bytes % 16 / 4);
+    const size_t ntiles = (nnv + kPackTileVecs - 1) / kPackTileVecs;
+    const size_t blocks = std::min(ntiles, g_widen_grid_cap);
+    if (t0) WIDEN_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(pair->fn, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       static_cast<const u32x4*>(src), nnv, static_cast<u32x4*>(dst),
+                       static_cast<u32x4*>(dst2), nwv, rem, ntiles, acc);
+    WIDEN_TRY(hipGetLastError());
+    if (t1) WIDEN_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    WIDEN_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    WIDEN_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) WIDEN_TRY(hipEventElapsedTime(kernel_ms, t0, t1));
+#undef WIDEN_TRY
+    sums[0] = host[0];
+    sums[1] = host[1];
+    return done(0);
+}
+
 // On-box variant exploration for the HBM sweep (tools only; the probe
 // uses g_sweep_variant).  Returns measured GB/s via *gbps.
 extern "C" int csp_hbm_bench(int device, int variant, size_t bytes, int reps,

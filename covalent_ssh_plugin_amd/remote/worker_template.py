@@ -37,6 +37,14 @@ Protocol (all frames: 8-byte big-endian length + payload):
              key is gone, or the checksum of the copy is not "sum", the
              argument fails, meta["arg_cache"]["miss"] names the entry and
              the dispatcher sends the task again with full frames).
+             With the executor option narrow_tensor_args a per-tensor entry
+             may carry "wire": a narrower dtype; its frame then holds the
+             elements at that type (numel * its element size bytes), lands
+             in a transient HBM buffer, and ONE csp_widen_checksum_dev call
+             widens it into the tensor (with "store": into the master and
+             the tensor) and yields the checksum of the wide bytes, which
+             is what "sum" announces; meta["arg_staging"] then counts
+             "widened", "wire_bytes" and "widen_ms".
              With the executor option pack_tensor_args the small tensor
              arguments of one electron share ONE entry {"device": true,
              "packed": [{dtype, shape, offset, nbytes}, ...], "nbytes":
@@ -188,6 +196,15 @@ NARROW_TARGETS = {
     "float64": (("float32", 0, 4),),
     "int64": (("uint8", 6, 1), ("int16", 5, 2), ("int32", 2, 4)),
     "int32": (("uint8", 6, 1), ("int16", 5, 2)),
+}
+# csp_widen_checksum_dev's pairs: (wire dtype, tensor dtype) -> (narrow kind,
+# wide kind, narrow element size, wide element size).  An argument entry with
+# "wire" (executor option narrow_tensor_args) arrives as the narrow bytes.
+WIDEN_PAIRS = {
+    ("bfloat16", "float32"): (4, 0, 2, 4), ("float32", "float64"): (0, 1, 4, 8),
+    ("int32", "int64"): (2, 3, 4, 8), ("int16", "int64"): (5, 3, 2, 8),
+    ("uint8", "int64"): (6, 3, 1, 8), ("int16", "int32"): (5, 2, 2, 4),
+    ("uint8", "int32"): (6, 2, 1, 4),
 }
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
@@ -391,6 +408,18 @@ def _load_gpu_lib():
             ctypes.c_size_t,
             ctypes.POINTER(ctypes.c_uint64),
             ctypes.POINTER(ctypes.c_uint32),
+            ctypes.POINTER(ctypes.c_float),
+        ]
+    if hasattr(lib, "csp_widen_checksum_dev"):
+        lib.csp_widen_checksum_dev.restype = ctypes.c_int
+        lib.csp_widen_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_int,
+            ctypes.c_int,
+            ctypes.c_void_p,
+            ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint64),
             ctypes.POINTER(ctypes.c_float),
         ]
     if GATHER_RESULTS and hasattr(lib, "csp_pack_gather_checksum_dev"):
@@ -1402,6 +1431,48 @@ def _device_arg_from_cache(lib, index, info, dtype, nbytes, key, stage, report):
     )
 
 
+def _widen_pair(lib, index, info):
+    """The WIDEN_PAIRS entry of an argument entry that carries ``"wire"``;
+    RuntimeError for a pair or a library that cannot widen it."""
+    pair = WIDEN_PAIRS.get((info["wire"], info["dtype"]))
+    if pair is None:
+        raise RuntimeError(
+            "argument buffer %d: no widening from wire type %r to %s"
+            % (index, info["wire"], info["dtype"])
+        )
+    if not hasattr(lib, "csp_widen_checksum_dev"):
+        raise RuntimeError(
+            "argument buffer %d arrived narrowed and the GPU library has no "
+            "csp_widen_checksum_dev" % index
+        )
+    return pair
+
+
+def _widen_device_arg(lib, index, pair, narrow, numel, dst, dst2, stage):
+    """ONE csp_widen_checksum_dev call: the ``numel`` narrow elements in the
+    uint8 CUDA buffer ``narrow`` widened into ``dst`` and, when given,
+    ``dst2``; returns [s0, s1] of the wide bytes."""
+    import ctypes
+
+    out = (ctypes.c_uint64 * 2)()
+    ms = ctypes.c_float()
+    rc = lib.csp_widen_checksum_dev(
+        ctypes.c_void_p(narrow.data_ptr()), numel, pair[0], pair[1],
+        ctypes.c_void_p(dst.data_ptr()),
+        ctypes.c_void_p(dst2.data_ptr() if dst2 is not None else None),
+        out, ctypes.byref(ms),
+    )
+    if rc != 0:
+        raise RuntimeError(
+            "argument buffer %d: csp_widen_checksum_dev failed: %s"
+            % (index, lib.csp_last_error().decode(errors="replace"))
+        )
+    stage["widened"] = stage.get("widened", 0) + 1
+    stage["wire_bytes"] = stage.get("wire_bytes", 0) + numel * pair[2]
+    stage["widen_ms"] = stage.get("widen_ms", 0.0) + ms.value
+    return [int(out[0]), int(out[1])]
+
+
 def _receive_device_arg(index, info, stage, report):
     """Persistent mode: take argument frame ``index`` off stdin straight
     into a fresh CUDA tensor.  Whatever goes wrong short of a broken
@@ -1413,7 +1484,12 @@ def _receive_device_arg(index, info, stage, report):
     ``"cache": {"key", "store": true}`` the frame lands in a new master
     first and the tensor is a verified copy of it; when the key is already
     cached, or the master does not fit, the frame lands in the tensor as
-    without a cache."""
+    without a cache.
+
+    With ``"wire"`` (narrow_tensor_args) the frame holds the elements at that
+    narrower type: it lands in a transient buffer, and ONE
+    csp_widen_checksum_dev call widens it into the new master and the tensor
+    (or the tensor alone) and yields the sum of the wide bytes."""
     global _arg_cache_resident
     import ctypes
 
@@ -1436,6 +1512,16 @@ def _receive_device_arg(index, info, stage, report):
         return _device_arg_from_cache(
             lib, index, info, dtype, nbytes, cache["key"], stage, report
         )
+    pair = None
+    frame_bytes = nbytes
+    if info.get("wire") is not None and nbytes:
+        try:
+            pair = _widen_pair(lib, index, info)
+        except RuntimeError:
+            if _read_frame(0) is None:  # its length is unknown here: the Python reader
+                os._exit(4)
+            raise
+        frame_bytes = nbytes // pair[3] * pair[2]
     key = None
     master = None
     if cache.get("store") and "sum" in info and nbytes:
@@ -1468,10 +1554,24 @@ def _receive_device_arg(index, info, stage, report):
     ptr = tensor.data_ptr() if (tensor is not None and nbytes) else 0
     if master is not None:
         ptr = master.data_ptr()
+    narrow = None
+    if pair is not None and alloc_error is None:
+        try:  # readable up to the next multiple of 16, as the kernel loads
+            narrow = torch.empty(
+                (frame_bytes + 15) // 16 * 16, dtype=torch.uint8, device="cuda"
+            )
+            ptr = narrow.data_ptr()
+        except Exception as e:  # noqa: BLE001 - e.g. out of HBM
+            alloc_error = e
+    if alloc_error is not None:
+        ptr = 0  # drain mode
+        if master is not None:
+            master = None
+            report["not_stored"].append(key)
     read_ms = ctypes.c_double()
     h2d_ms = ctypes.c_double()
     rc = lib.csp_h2d_stream_fd(
-        0, ctypes.c_void_p(ptr), nbytes, STREAM_CHUNK, -1,
+        0, ctypes.c_void_p(ptr), frame_bytes, STREAM_CHUNK, -1,
         ctypes.byref(read_ms), ctypes.byref(h2d_ms),
     )
     stage["read_ms"] += read_ms.value
@@ -1495,11 +1595,25 @@ def _receive_device_arg(index, info, stage, report):
     stage["mode"] = "pinned-h2d"
     stage["tensors"] += 1
     stage["bytes"] += nbytes
-    if master is None:
+    if narrow is not None:
+        # one pass: the master, the electron's tensor and the sum of both
+        got = _widen_device_arg(
+            lib, index, pair, narrow, nbytes // pair[3],
+            tensor if master is None else master,
+            None if master is None else tensor, stage,
+        )
+        del narrow
+        if master is None:
+            if "sum" in info:
+                stage["verified"] += 1
+                _compare_arg_sum(index, got, info, nbytes)
+            return tensor
+    elif master is None:
         _verify_device_arg(lib, index, tensor, nbytes, info, stage)
         return tensor
-    # the copy that the electron gets is also the verification pass
-    got = _copy_from_master(lib, index, tensor, master, nbytes)
+    else:
+        # the copy that the electron gets is also the verification pass
+        got = _copy_from_master(lib, index, tensor, master, nbytes)
     stage["verified"] += 1
     _compare_arg_sum(index, got, info, nbytes)  # a mismatch drops the master
     _arg_cache[key] = (master, nbytes, got)
@@ -2107,6 +2221,32 @@ def _device_args_in_child(frames, meta_list, stage):
             continue
         dtype = getattr(torch, info["dtype"])
         t0 = time.monotonic()
+        if info.get("wire") is not None and len(frames[i]):
+            # narrow_tensor_args: the narrow frame into a rounded buffer, then
+            # the same single widening call as in persistent mode
+            pair = _widen_pair(lib, i, info)
+            tensor = torch.empty(info["shape"], dtype=dtype, device="cuda")
+            wire_bytes = tensor.numel() * pair[2]
+            if len(frames[i]) != wire_bytes:
+                raise RuntimeError(
+                    "argument buffer %d: the narrowed frame has %d bytes, its "
+                    "entry announces %d" % (i, len(frames[i]), wire_bytes)
+                )
+            narrow = torch.empty((wire_bytes + 15) // 16 * 16, dtype=torch.uint8, device="cuda")
+            narrow[:wire_bytes].copy_(torch.frombuffer(frames[i], dtype=torch.uint8))
+            torch.cuda.synchronize()
+            stage["h2d_ms"] += (time.monotonic() - t0) * 1000
+            nbytes = tensor.numel() * tensor.element_size()
+            got = _widen_device_arg(lib, i, pair, narrow, tensor.numel(), tensor, None, stage)
+            del narrow
+            stage["mode"] = "isolated-copy"
+            stage["tensors"] += 1
+            stage["bytes"] += nbytes
+            if "sum" in info:
+                stage["verified"] += 1
+                _compare_arg_sum(i, got, info, nbytes)
+            frames[i] = tensor
+            continue
         if len(frames[i]) == 0:
             tensor = torch.empty(info["shape"], dtype=dtype, device="cuda")
         else:

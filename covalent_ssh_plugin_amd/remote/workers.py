@@ -18,6 +18,7 @@ import hashlib
 import os
 import struct
 import threading
+import time
 import weakref
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
@@ -214,6 +215,62 @@ def threaded_checksum(buf, chunk_bytes: int = ARG_CACHE_CHUNK, threads: Optional
     return s0 & mask, s1 & mask
 
 
+def narrow_arg(view, dtype: str, chunk_bytes: int = ARG_CACHE_CHUNK,
+               threads: Optional[int] = None, stats: Optional[dict] = None):
+    """``narrow_tensor_args``: the contiguous bytes ``view`` of a ``dtype``
+    tensor as ``(wire dtype name, bytearray)`` at the narrowest of
+    ``csp_narrow_checksum_dev``'s targets that gives every element back bit for
+    bit (the worker widens with ``csp_widen_checksum_dev``), or ``None`` when
+    no target does, the dtype has none or ``libcsp_io.so`` is not loaded.
+    ``native_io.narrow`` runs over ``chunk_bytes`` pieces on the thread pool
+    and the pieces' ``bad`` words are ORed.  An integer takes a test pass and
+    then a narrow pass at the tightest fitting target; a float takes one pass,
+    and its buffer is dropped when ``bad`` is set.  ``stats`` gets
+    ``arg_narrowed``, ``arg_narrow_saved_bytes`` and ``arg_narrow_ms`` (the
+    attempts that came out inexact included)."""
+    lib = native_io.load()
+    targets = native_io.NARROW_TARGETS.get(dtype)
+    if lib is None or not hasattr(lib, "csp_io_narrow") or not targets:
+        return None
+    started = time.perf_counter()
+    es = native_io.NARROW_ELEM_SIZE[dtype]
+    nbytes = memoryview(view).nbytes
+    pieces = _chunks(nbytes, max(es, chunk_bytes // es * es))
+
+    def run(dst_kind, out):
+        nes = native_io.NARROW_ELEM_SIZE[dst_kind]
+        bad = 0
+        for b in _map(
+            lambda p: native_io.narrow(view, p[1] // es, dtype, dst_kind, out, p[0],
+                                       p[0] // es * nes),
+            pieces, threads,
+        ):
+            bad |= b
+        return bad
+
+    wire = out = None
+    if dtype.startswith("int"):
+        fits = native_io.narrow_fits(dtype, run(targets[-1], None))
+        if fits:
+            wire = fits[0]
+            out = bytearray(nbytes // es * native_io.NARROW_ELEM_SIZE[wire])
+            run(wire, out)
+    else:
+        out = bytearray(nbytes // es * native_io.NARROW_ELEM_SIZE[targets[0]])
+        if run(targets[0], out) == 0:
+            wire = targets[0]
+    if stats is not None:
+        stats["arg_narrow_ms"] = (
+            stats.get("arg_narrow_ms", 0.0) + (time.perf_counter() - started) * 1e3
+        )
+        if wire is not None:
+            stats["arg_narrowed"] = stats.get("arg_narrowed", 0) + 1
+            stats["arg_narrow_saved_bytes"] = (
+                stats.get("arg_narrow_saved_bytes", 0) + nbytes - len(out)
+            )
+    return None if wire is None else (wire, out)
+
+
 _key_memo: Dict[int, tuple] = {}  # id(tensor) -> (weakref, guard, key)
 
 
@@ -399,6 +456,8 @@ def extract_arg_buffers(
     patch_max_fraction: Optional[float] = None,
     rebase: bool = False,
     retain: bool = False,
+    narrow: bool = False,
+    narrow_stats: Optional[dict] = None,
 ):
     """Pull large contiguous CPU torch tensors out of (args, kwargs) and
     replace them with out-of-band buffer markers (the request-direction
@@ -453,7 +512,18 @@ def extract_arg_buffers(
 
     ``retain`` (the executor's ``retain_tensor_results``, with ``rebase``):
     such an entry may also be rebased with an EMPTY delta, the case of a
-    subset or a reordering of what a retained result arena holds."""
+    subset or a reordering of what a retained result arena holds.
+
+    ``narrow`` (the executor's ``narrow_tensor_args``, with ``to_device``): a
+    float32, float64, int32 or int64 tensor of at least ``threshold`` bytes on
+    the per-tensor path that :func:`narrow_arg` can narrow losslessly gains
+    ``"wire": <narrow dtype name>`` and travels as the narrow buffer,
+    ``numel * narrow element size`` bytes; ``dtype``, ``shape``, ``sum`` and
+    ``cache.key`` stay those of the wide tensor, and the worker widens on the
+    GPU.  A cacheable entry is only marked here and narrowed by
+    :meth:`_ArgCacheSend.frames` when its bytes actually travel; its buffer
+    stays the wide view.  ``narrow_stats``: see :func:`narrow_arg`.  Without
+    ``libcsp_io.so`` nothing is narrowed."""
     import sys
 
     if "torch" not in sys.modules:
@@ -488,6 +558,16 @@ def extract_arg_buffers(
                 info["sum"] = [int(sums[0]), int(sums[1])]
                 if cacheable:
                     info["cache"] = {"key": tensor_content_key(t, view)}
+                if narrow and nbytes >= max(1, threshold) and (
+                    info["dtype"] in native_io.NARROW_TARGETS
+                ):
+                    if cacheable:  # decided when the bytes travel, not for a ref
+                        info["cache"]["narrow"] = True
+                    else:
+                        narrowed = narrow_arg(view, info["dtype"], stats=narrow_stats)
+                        if narrowed is not None:
+                            info["wire"] = narrowed[0]
+                            buffers[-1] = (narrowed[1], (src_t, view))
         buffer_meta.append(info)
         return ("__csp_tensor_buffer_v1__", len(buffers) - 1)
 
@@ -874,6 +954,9 @@ class _ArgCacheSend:
         #: -1, delta FrameParts)`` when the last :meth:`frames` sent it as a
         #: rebase, else None
         self.rebases = [None] * len(entries)
+        #: per entry ``(wire dtype name, narrow buffer)`` while the last
+        #: :meth:`frames` has it to send narrowed (``narrow_tensor_args``)
+        self.narrowed = [None] * len(entries)
         #: worker name -> content key, for every name the last :meth:`frames`
         #: put on the wire in place of a key (``retain_tensor_results``)
         self.sent_as = {}
@@ -991,6 +1074,7 @@ class _ArgCacheSend:
         ]
         self.patches = [None] * len(self.entries)
         self.rebases = [None] * len(self.entries)
+        self.narrowed = [None] * len(self.entries)
         self.sent_as = {}
         wire = []
         for index, (info, key, ref) in enumerate(zip(self.entries, self.keys, self.refs)):
@@ -1024,6 +1108,13 @@ class _ArgCacheSend:
                         {"key": self._wire(key), "ref": True} if ref
                         else {"key": key, "store": True}
                     )
+                    if not ref and cache.get("narrow"):
+                        # narrow_tensor_args: these bytes travel, so narrow now
+                        self.narrowed[index] = narrow_arg(
+                            self.views[index], info["dtype"], stats=self.cache_stats
+                        )
+                        if self.narrowed[index] is not None:
+                            info["wire"] = self.narrowed[index][0]
             wire.append(info)
         yield cloudpickle.dumps(dict(self.base, arg_buffers=wire))
         for index, (view, key, ref) in enumerate(zip(self.views, self.keys, self.refs)):
@@ -1034,6 +1125,9 @@ class _ArgCacheSend:
             if rebase is not None:
                 yield rebase[3]
                 self._touch(rebase[0])  # the base stays, and was used
+            elif self.narrowed[index] is not None:
+                yield self.narrowed[index][1]
+                self.narrowed[index] = None  # sent: the buffer may go
             else:
                 yield view if patch is None else patch[2]
             if patch is not None:

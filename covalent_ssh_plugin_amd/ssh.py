@@ -210,6 +210,16 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # verifies the narrow bytes and widens them back, bit for bit.  A tensor
     # with one element that does not fit travels whole, as without the option.
     "narrow_tensor_results": False,
+    # The argument side of it (needs device_tensor_args): a large contiguous
+    # CPU tensor argument of float32, float64, int32 or int64 on the
+    # per-tensor path is narrowed on the dispatcher to the narrowest width
+    # that loses nothing (an int64 edge_index or embedding ids as uint8, int16
+    # or int32, float32 from a bf16 pipeline as bfloat16, float64 that holds
+    # float32 values as float32).  The worker lands the narrow bytes in HBM
+    # and one kernel launch widens them, fills the cached master as well and
+    # yields the checksum announced for the tensor's own bytes.  A tensor with
+    # one element that does not fit travels whole, as without the option.
+    "narrow_tensor_args": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth
     # electron per worker; 0 = off (keeps the no-op hot path minimal).
@@ -415,6 +425,7 @@ class SSHExecutor(RemoteExecutor):
         delta_tensor_results: Optional[bool] = None,
         gather_tensor_results: Optional[bool] = None,
         narrow_tensor_results: Optional[bool] = None,
+        narrow_tensor_args: Optional[bool] = None,
         cpu_workers: Optional[int] = None,
         gpu_telemetry_every: Optional[int] = None,
         task_timeout: Optional[float] = None,
@@ -577,6 +588,14 @@ class SSHExecutor(RemoteExecutor):
                 "narrow_tensor_results needs persistent_workers or isolate_tasks: "
                 "only the worker channel carries result tensors out of band"
             )
+        self.narrow_tensor_args = bool(
+            _conf("narrow_tensor_args", narrow_tensor_args, default=False)
+        )
+        if self.narrow_tensor_args and not self.device_tensor_args:
+            raise ValueError(
+                "narrow_tensor_args needs device_tensor_args=True: it narrows the "
+                "tensor arguments that are widened in the worker's HBM"
+            )
         self.cpu_workers = int(_conf("cpu_workers", cpu_workers))
         self.gpu_telemetry_every = int(
             _conf("gpu_telemetry_every", gpu_telemetry_every, default=0) or 0
@@ -632,6 +651,12 @@ class SSHExecutor(RemoteExecutor):
             # delta against an argument, and the bytes the delta left out
             "result_deltas": 0,
             "result_delta_bytes_saved": 0,
+            # narrow_tensor_args: arguments sent at a narrower width, the
+            # bytes that left out, and the dispatcher's time in the narrowing
+            # passes (the attempts that came out inexact included)
+            "arg_narrowed": 0,
+            "arg_narrow_saved_bytes": 0,
+            "arg_narrow_ms": 0.0,
         }
 
     # ------------------------------------------------------------------
@@ -1492,6 +1517,11 @@ class SSHExecutor(RemoteExecutor):
                             ),
                             **({"rebase": True} if self.rebase_tensor_args else {}),
                             **({"retain": True} if self.retain_tensor_results else {}),
+                            **(
+                                {"narrow": True, "narrow_stats": self.counters}
+                                if self.narrow_tensor_args
+                                else {}
+                            ),
                         )
                     )
                     function_blob = cloudpickle.dumps((function, s_args, s_kwargs))

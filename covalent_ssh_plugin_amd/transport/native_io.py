@@ -68,6 +68,12 @@ def load(path: str = "") -> Optional[ctypes.CDLL]:
     lib.csp_io_checksum.argtypes = [
         ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
     ]
+    if hasattr(lib, "csp_io_narrow"):  # a library built before narrow_tensor_args
+        lib.csp_io_narrow.restype = ctypes.c_int
+        lib.csp_io_narrow.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint64),
+        ]
     _lib = lib
     return lib
 
@@ -144,6 +150,65 @@ def checksum(buf, nbytes: Optional[int] = None, offset: int = 0):
         carrier = (ctypes.c_char * nbytes).from_buffer(window)
         lib.csp_io_checksum(ctypes.addressof(carrier), nbytes, out)
     return int(out[0]), int(out[1])
+
+
+# element kinds of :func:`narrow`, by torch dtype name (the library's
+# ``CSP_KIND_*``), their sizes, and every source's targets, narrowest first
+NARROW_KINDS = {"float32": 0, "float64": 1, "int32": 2, "int64": 3, "bfloat16": 4, "int16": 5,
+                "uint8": 6}
+NARROW_ELEM_SIZE = {"float32": 4, "float64": 8, "int32": 4, "int64": 8, "bfloat16": 2,
+                    "int16": 2, "uint8": 1}
+NARROW_TARGETS = {"float32": ("bfloat16",), "float64": ("float32",),
+                  "int32": ("uint8", "int16"), "int64": ("uint8", "int16", "int32")}
+NARROW_FLAG = 1 << 63
+
+
+def narrow_fits(src: str, bad: int) -> tuple:
+    """The targets of ``src``, narrowest first, that a ``bad`` word from
+    :func:`narrow` (or from ``csp_narrow_checksum_kernel``) leaves exact: the
+    same table as ``narrow_fits`` in ``csp_gpu.hip``."""
+    mag, neg = bad & ~NARROW_FLAG, bool(bad & NARROW_FLAG)
+    if src in ("float32", "float64"):
+        return NARROW_TARGETS[src] if bad == 0 else ()
+    limit = {"uint8": 1 << 8, "int16": 1 << 15, "int32": 1 << 31}
+    return tuple(
+        d for d in NARROW_TARGETS.get(src, ())
+        if mag < limit[d] and not (d == "uint8" and neg)
+    )
+
+
+def narrow(src, numel: int, src_kind: str, dst_kind: str, dst=None, src_offset: int = 0,
+           dst_offset: int = 0) -> int:
+    """One pass of ``csp_io_narrow`` over ``numel`` elements of ``src_kind``
+    at byte ``src_offset`` of ``src``; returns the ``bad`` word of that piece
+    (0: every element narrows to ``dst_kind`` exactly; see :func:`narrow_fits`).
+    With ``dst`` (a writable buffer) the narrowed elements are written at its
+    byte ``dst_offset``, whatever the verdict.  ctypes drops the GIL for the
+    call."""
+    lib = load()
+    if lib is None or not hasattr(lib, "csp_io_narrow"):
+        raise RuntimeError(f"{_LIB_NAME} is not built")
+    nbytes = numel * NARROW_ELEM_SIZE[src_kind]
+    window = memoryview(src).cast("B")[src_offset : src_offset + nbytes]
+    if window.nbytes != nbytes:
+        raise ValueError("range outside the buffer")
+    if window.readonly:
+        keep = source = bytes(window)  # ctypes cannot borrow a read-only buffer
+    else:
+        keep = (ctypes.c_char * nbytes).from_buffer(window) if nbytes else None
+        source = ctypes.addressof(keep) if nbytes else None
+    out_addr, out_keep = (None, None)
+    if dst is not None:
+        out_addr, out_keep = _address(dst, dst_offset, numel * NARROW_ELEM_SIZE[dst_kind])
+    bad = ctypes.c_uint64(0)
+    rc = lib.csp_io_narrow(
+        source, numel, NARROW_KINDS.get(src_kind, -1), NARROW_KINDS.get(dst_kind, -1),
+        out_addr or None, ctypes.byref(bad),
+    )
+    del keep, out_keep
+    if rc != 0:
+        raise ValueError(f"no narrowing from {src_kind} to {dst_kind}")
+    return int(bad.value)
 
 
 def alloc_buffer(nbytes: int):
