@@ -35,6 +35,10 @@ gfx950 only) provides:
 * ``csp_narrow_checksum_dev`` — a contiguous float32, float64, int32 or int64
   device tensor tested for a lossless narrower form, written in that form and
   checksummed by one launch (``narrow_tensor_results``),
+* ``csp_pack_narrow_probe_dev`` and ``csp_pack_narrow_checksum_dev`` — the
+  same inside the packed arena: one launch tests all candidate tensors, one
+  fills and sums an arena of narrowed segments and plain copies
+  (``pack_tensor_results`` with ``narrow_tensor_results``),
 * ``csp_widen_checksum_dev`` — the inverse for arguments: narrow bytes in HBM
   widened into one or two destinations and checksummed by one launch
   (``narrow_tensor_args``),
@@ -76,6 +80,20 @@ class PackGatherSeg(ctypes.Structure):
         ("ndim", ctypes.c_uint32),
         ("shape", ctypes.c_uint64 * 8),
         ("stride", ctypes.c_uint64 * 8),
+    ]
+
+
+class PackNarrowSeg(ctypes.Structure):
+    """``CspPackNarrowSeg``: one segment of ``csp_pack_narrow_probe_dev`` and
+    ``csp_pack_narrow_checksum_dev``.  ``dst_kind == -1`` is a copy of
+    ``numel`` bytes; otherwise ``numel`` elements of ``src_kind``."""
+
+    _fields_ = [
+        ("src", ctypes.c_void_p),
+        ("numel", ctypes.c_uint64),
+        ("src_kind", ctypes.c_int32),
+        ("dst_kind", ctypes.c_int32),
+        ("dst_off", ctypes.c_uint64),
     ]
 
 
@@ -266,6 +284,29 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_narrow_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_narrow_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_pack_narrow_probe_dev.restype = ctypes.c_int
+    lib.csp_pack_narrow_probe_dev.argtypes = [
+        ctypes.POINTER(PackNarrowSeg),
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_pack_narrow_checksum_dev.restype = ctypes.c_int
+    lib.csp_pack_narrow_checksum_dev.argtypes = [
+        ctypes.POINTER(PackNarrowSeg),
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_pack_narrow_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_pack_narrow_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_pack_narrow_probe_nt.restype = ctypes.c_int
+    lib.csp_pack_narrow_probe_nt.argtypes = [ctypes.c_int]
+    lib.csp_narrow_fits.restype = ctypes.c_uint32
+    lib.csp_narrow_fits.argtypes = [ctypes.c_int, ctypes.c_uint64]
     lib.csp_widen_checksum_dev.restype = ctypes.c_int
     lib.csp_widen_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -820,6 +861,116 @@ def narrow_checksum_grid_cap(cap: int = 0) -> int:
     """Tools only: set the grid cap of :func:`narrow_checksum_device` (0
     restores the shipped default).  Returns the cap in effect."""
     return int(load().csp_narrow_checksum_grid_cap(int(cap)))
+
+
+def _pack_narrow_table(segments):
+    """``(src_ptr, numel, src, dst, dst_off)`` rows as ``PackNarrowSeg``;
+    ``dst`` ``""`` is a copy of ``numel`` bytes."""
+    table = (PackNarrowSeg * max(1, len(segments)))()
+    for row, (ptr, numel, src, dst, off) in zip(table, segments):
+        row.src = int(ptr) or None
+        row.numel = int(numel)
+        row.src_kind = NARROW_KINDS.get(src, -2) if src else 0
+        row.dst_kind = NARROW_KINDS.get(dst, -2) if dst else -1
+        row.dst_off = int(off)
+    return table
+
+
+def _fits_of(lib, src: str, bad: int) -> tuple:
+    mask = lib.csp_narrow_fits(NARROW_KINDS.get(src, -1), bad)
+    return tuple(d for d in NARROW_TARGETS.get(src, ()) if mask >> NARROW_KINDS[d] & 1)
+
+
+def pack_narrow_probe_device(segments) -> dict:
+    """Test every ``(src_ptr, numel, src)`` of ``segments``, contiguous
+    16-byte aligned device tensors of a dtype name in ``NARROW_TARGETS``, for
+    lossless narrowing in ONE kernel launch that stores one word per segment
+    (``pack_tensor_results`` with ``narrow_tensor_results``).  Returns
+    ``{"bad", "fits", "kernel_ms"}``: per segment the raw word, and the tuple of
+    its targets, narrowest first, that give every element back bit for bit.
+    A null or misaligned pointer, a dtype without targets or a segment above
+    16 GiB raises ``GpuLibError`` naming the segment and launches nothing.
+    Runs on the library's copy stream; sources written on another stream must
+    be complete first."""
+    lib = load()
+    n = len(segments)
+    table = _pack_narrow_table([(s[0], s[1], s[2], "", 0) for s in segments])
+    bad = (ctypes.c_uint64 * max(1, n))()
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_pack_narrow_probe_dev(table, n, bad, ctypes.byref(kernel_ms)),
+        "csp_pack_narrow_probe_dev",
+    )
+    words = [int(bad[k]) for k in range(n)]
+    return {
+        "bad": words,
+        "fits": [_fits_of(lib, s[2], w) for s, w in zip(segments, words)],
+        "kernel_ms": kernel_ms.value,
+    }
+
+
+def pack_narrow_layout(segments):
+    """``(offsets, total)`` of an arena of ``(src_ptr, numel, src, dst)``
+    segments: :func:`pack_layout` over the bytes each occupies in the arena,
+    ``numel`` bytes for a copy (``dst == ""``), ``numel`` elements of ``dst``
+    otherwise."""
+    return pack_layout(
+        [s[1] * NARROW_ELEM_SIZE[s[3]] if s[3] else s[1] for s in segments]
+    )
+
+
+def pack_narrow_checksum_device(segments, arena_ptr: int, arena_bytes: int) -> dict:
+    """Fill the 16-byte aligned device arena at ``arena_ptr`` from
+    ``segments``, ``(src_ptr, numel, src, dst, dst_off)`` each, and checksum it
+    in ONE kernel launch.  ``dst == ""`` copies ``numel`` bytes from any
+    alignment; otherwise the ``numel`` contiguous ``src`` elements at the
+    16-byte aligned ``src_ptr`` are narrowed to ``dst`` (a pair of
+    :func:`narrow_checksum_device`).  Offsets and ``arena_bytes`` follow
+    :func:`pack_narrow_layout`; the padding is stored as zero.  Returns
+    ``{"sum", "bad", "fits", "kernel_ms"}``: ``sum`` is :func:`checksum_device`
+    of the arena; ``fits[k]`` is what the pass that wrote segment ``k`` found
+    exact (``None`` for a copy) — when ``dst`` is not in it the segment's
+    bytes mean nothing.  A layout violation, an unserved pair, a null or
+    misaligned pointer or a source that overlaps the arena raises
+    ``GpuLibError`` naming the segment and launches nothing.  Runs on the
+    library's copy stream; sources written on another stream must be complete
+    first."""
+    lib = load()
+    n = len(segments)
+    table = _pack_narrow_table(segments)
+    out = (ctypes.c_uint64 * 2)()
+    bad = (ctypes.c_uint64 * max(1, n))()
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_pack_narrow_checksum_dev(
+            table, n, ctypes.c_void_p(arena_ptr or None), arena_bytes, out, bad,
+            ctypes.byref(kernel_ms),
+        ),
+        "csp_pack_narrow_checksum_dev",
+    )
+    words = [int(bad[k]) for k in range(n)]
+    return {
+        "sum": (int(out[0]), int(out[1])),
+        "bad": words,
+        "fits": [_fits_of(lib, s[2], w) if s[3] else None for s, w in zip(segments, words)],
+        "kernel_ms": kernel_ms.value,
+    }
+
+
+def pack_narrow_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`pack_narrow_probe_device` and
+    :func:`pack_narrow_checksum_device` (0 restores the shipped default).
+    Returns the cap in effect."""
+    return int(load().csp_pack_narrow_checksum_grid_cap(int(cap)))
+
+
+def pack_narrow_probe_nt(on: int = -1) -> int:
+    """Tools only: 1 makes :func:`pack_narrow_probe_device` load
+    nontemporally, 0 plainly, -1 restores the shipped default.  Returns the
+    value in effect."""
+    return int(load().csp_pack_narrow_probe_nt(int(on)))
 
 
 def widen_checksum_device(

@@ -4444,6 +4444,15 @@ __device__ __forceinline__ u32x4 narrow_load_tail(const u32x4* p, unsigned int r
         if (j < rem) v[j] = w[j];
     return v;
 }
+// the same for a source that came out of a table in memory (see CSP_GLOBAL)
+__device__ __forceinline__ u32x4 narrow_load_tail(const CSP_GLOBAL u32x4* p, unsigned int rem) {
+    const CSP_GLOBAL unsigned int* w = reinterpret_cast<const CSP_GLOBAL unsigned int*>(p);
+    u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (unsigned int j = 0; j < 3; ++j)
+        if (j < rem) v[j] = w[j];
+    return v;
+}
 
 // orders a wave's LDS writes before its LDS reads (and the reverse) for the
 // compiler; the hardware completes one wave's LDS operations in order
@@ -4452,6 +4461,55 @@ __device__ __forceinline__ void narrow_strip_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// One wave's four steps of output tile TILE, in trips of U steps: the body both
+// narrowing kernels share, written once.  It is a textual fragment, not a
+// function: expanded inside csp_narrow_checksum_kernel the compiler sees that
+// kernel's own loop and keeps its register allocation, which an inlined
+// function did not (profiles/packed_narrowed_results.md).  The scope supplies
+// N = Narrow<SRC, DST>, R, U and piece_t; src, nsv (source vectors wholly
+// below numel), rem (4-byte words of the partial one after them), dst, nov
+// (output vectors, the zero-padded last one included); strip, LDS of
+// [4 waves][U or more][64 vectors]; lane, wave; s0, t, bad.  WORD_BASE: the
+// index of dst's first word in what is summed (0 for a buffer of its own,
+// dst_off / 4 inside an arena).  step0 depends on the tile, the wave and the
+// trip alone: every branch on it is wave-uniform, and all 64 lanes reach the
+// strip together.
+#define CSP_NARROW_WAVE_STEPS(TILE, WORD_BASE)                                                  \
+    for (int j = 0; j < kNarrowStepsPerWave; j += U) {                                          \
+        const size_t step0 = ((TILE) * 4 + wave) * kNarrowStepsPerWave + j;                     \
+        if (step0 * kNarrowStepVecs >= nov) break; /* the last tile's unused steps */           \
+        const size_t sv0 = step0 * kNarrowStepVecs * R + lane;                                  \
+        u32x4 v[U * R];                                                                         \
+        if ((step0 + U) * kNarrowStepVecs * R <= nsv) {                                         \
+            _Pragma("unroll") for (int i = 0; i < U * R; ++i)                                   \
+                v[i] = __builtin_nontemporal_load(&src[sv0 + i * kNarrowStepVecs]);             \
+        } else { /* the trip that holds the source's end */                                     \
+            _Pragma("unroll") for (int i = 0; i < U * R; ++i) {                                 \
+                const size_t sv = sv0 + i * kNarrowStepVecs;                                    \
+                v[i] = u32x4{0u, 0u, 0u, 0u};                                                   \
+                if (sv < nsv) v[i] = __builtin_nontemporal_load(&src[sv]);                      \
+                else if (sv == nsv && rem != 0) v[i] = narrow_load_tail(src + nsv, rem);        \
+            }                                                                                   \
+        }                                                                                       \
+        if (dst == nullptr) { /* probe: uniform for the whole grid */                           \
+            _Pragma("unroll") for (int i = 0; i < U * R; ++i)(void) N::apply(v[i], bad);        \
+            continue;                                                                           \
+        }                                                                                       \
+        _Pragma("unroll") for (int i = 0; i < U * R; ++i)                                       \
+            reinterpret_cast<piece_t*>(&strip[wave][i / R][0])[(i % R) * kNarrowStepVecs +      \
+                                                                lane] = N::apply(v[i], bad);    \
+        narrow_strip_sync();                                                                    \
+        _Pragma("unroll") for (int u = 0; u < U; ++u) {                                         \
+            const size_t ov = (step0 + u) * kNarrowStepVecs + lane;                             \
+            const u32x4 o = strip[wave][u][lane];                                               \
+            if (ov < nov) {                                                                     \
+                __builtin_nontemporal_store(o, &dst[ov]);                                       \
+                checksum_add(s0, t, o, (WORD_BASE) + (unsigned int)(ov * 4));                   \
+            }                                                                                   \
+        }                                                                                       \
+        narrow_strip_sync(); /* the next trip overwrites the strip */                           \
+    }
 
 // nsv: source vectors wholly below numel; rem: 4-byte words of the partial
 // one after them; nov: output vectors, the zero-padded last one included
@@ -4469,47 +4527,7 @@ __global__ __launch_bounds__(256) void csp_narrow_checksum_kernel(
     const unsigned int wave = threadIdx.x >> 6;
     unsigned long long s0 = 0, t = 0, bad = 0;
     for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        // step0 depends on the tile, the wave and j alone: every branch on it
-        // is wave-uniform, and all 64 lanes reach the strip together
-        for (int j = 0; j < kNarrowStepsPerWave; j += U) {
-            const size_t step0 = (tile * 4 + wave) * kNarrowStepsPerWave + j;
-            if (step0 * kNarrowStepVecs >= nov) break;  // the last tile's unused steps
-            const size_t sv0 = step0 * kNarrowStepVecs * R + lane;
-            u32x4 v[U * R];
-            if ((step0 + U) * kNarrowStepVecs * R <= nsv) {
-#pragma unroll
-                for (int i = 0; i < U * R; ++i)
-                    v[i] = __builtin_nontemporal_load(&src[sv0 + i * kNarrowStepVecs]);
-            } else {  // the trip that holds the source's end
-#pragma unroll
-                for (int i = 0; i < U * R; ++i) {
-                    const size_t sv = sv0 + i * kNarrowStepVecs;
-                    v[i] = u32x4{0u, 0u, 0u, 0u};
-                    if (sv < nsv) v[i] = __builtin_nontemporal_load(&src[sv]);
-                    else if (sv == nsv && rem != 0) v[i] = narrow_load_tail(src + nsv, rem);
-                }
-            }
-            if (dst == nullptr) {  // probe: uniform for the whole grid
-#pragma unroll
-                for (int i = 0; i < U * R; ++i) (void)N::apply(v[i], bad);
-                continue;
-            }
-#pragma unroll
-            for (int i = 0; i < U * R; ++i)
-                reinterpret_cast<piece_t*>(&strip[wave][i / R][0])[(i % R) * kNarrowStepVecs +
-                                                                    lane] = N::apply(v[i], bad);
-            narrow_strip_sync();
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t ov = (step0 + u) * kNarrowStepVecs + lane;
-                const u32x4 o = strip[wave][u][lane];
-                if (ov < nov) {
-                    __builtin_nontemporal_store(o, &dst[ov]);
-                    checksum_add(s0, t, o, (unsigned int)(ov * 4));
-                }
-            }
-            narrow_strip_sync();  // the next trip overwrites the strip
-        }
+        CSP_NARROW_WAVE_STEPS(tile, 0u)
     }
     unsigned long long s1 = t + s0;
 
@@ -4717,6 +4735,582 @@ extern "C" int csp_narrow_checksum_dev(const void* src, size_t numel, int src_ki
     sums[1] = host[1];
     *fits = narrow_fits(src_kind, host[2]);
     return done(0);
+}
+
+// ---------------------------------------------------------------------------
+// Narrowing inside the packed arena: one probe, then one fill-and-sum launch
+// ---------------------------------------------------------------------------
+//
+// The small CUDA tensors of a result share one arena (csp_pack_dev's layout).
+// A state_dict of float32 tensors upcast from bf16, or a dict of int64 index
+// tensors, could cross the pipe at a half to an eighth of those bytes, but
+// csp_narrow_checksum_dev serves one tensor per launch, sums its own buffer
+// only, and gives its verdict after the call, while the arena's layout
+// depends on every verdict.  Two kernels close that:
+//
+//   - csp_pack_narrow_probe_kernel reads all candidates once and stores one
+//     `bad` word per segment (narrow_fits()'s encoding), nothing else.  Units
+//     are 16 KiB tiles of the SOURCE, found by the pack kernels' wave-uniform
+//     binary search over a host-built prefix.  A lane issues its four 16-byte
+//     loads before the first use; each wave ORs its `bad` by shuffles and lane
+//     0 issues one atomicOr, only for a non-zero word: exact data issues no
+//     atomic at all.  No LDS, no workgroup barrier.  The loads are plain: the
+//     second kernel reads the same lines next (kPackNarrowProbeNt below);
+//   - csp_pack_narrow_checksum_kernel fills and sums the narrow arena.  Units
+//     are 16 KiB tiles of each segment's OUTPUT; a workgroup branches
+//     uniformly per unit: COPY is pack_checksum_tile<ALIGN>, as in
+//     csp_pack_checksum_kernel (any alignment, any dtype, and the segments
+//     the probe found inexact); NARROW is CSP_NARROW_WAVE_STEPS, the
+//     body csp_narrow_checksum_kernel runs, with the arena-global word index
+//     dst_off / 4.  One strip array of 4 waves x 2 x 1 KiB serves all pairs;
+//     strips are wave-private, so no unit needs a workgroup barrier.  The
+//     per-lane u64 sums are carried across units of all kinds and end in
+//     shuffles, LDS and one atomic pair per workgroup.  `bad` is reduced per
+//     unit per wave and ORed into bad_out[seg] as in the probe, so the call
+//     that wrote the bytes also confirms the verdict: a source that changed
+//     after the probe is caught, not sent wrong.
+//
+// Every arena byte is written exactly once, the zero padding after each
+// segment included, and nothing past arena_bytes; nothing past a source's
+// last element is read.
+#define CSP_PACK_NARROW_COPY (-1)  // dst_kind of a segment that is only copied
+
+// One segment of the two entry points below.  Plain C, fixed layout, 32
+// bytes.  numel counts elements of src_kind; for a copy it counts bytes and
+// src_kind is not looked at.  The probe ignores dst_kind and dst_off.
+struct CspPackNarrowSeg {
+    const void* src;
+    uint64_t numel;
+    int32_t src_kind;  // CSP_KIND_F32, F64, I32 or I64
+    int32_t dst_kind;  // a target of src_kind, or CSP_PACK_NARROW_COPY
+    uint64_t dst_off;
+};
+static_assert(sizeof(CspPackNarrowSeg) == 32, "the layout the bindings declare");
+
+// `what`: probe: the source kind; pack: src_kind * 8 + dst_kind, or
+// kPackNarrowCopyUnit.  n: source vectors wholly below numel (a copy: bytes)
+struct PackNarrowEntry {
+    const unsigned char* src;
+    unsigned long long dst_off;
+    unsigned long long n;
+    unsigned long long nov;         // output vectors, the padded last one included
+    unsigned long long unit_begin;  // units owned by the entries before this one
+    unsigned int what;
+    unsigned int rem;  // 4-byte words of the partial source vector after n
+    unsigned int seg;  // the segment's index in bad_out
+    unsigned int reserved;
+};
+static const unsigned int kPackNarrowCopyUnit = 0xFFu;
+#define CSP_PACK_NARROW_WHAT(S, D) (unsigned int)(CSP_KIND_##S * 8 + CSP_KIND_##D)
+
+// a wave's `bad` of one unit into the segment's word; silent when exact
+__device__ __forceinline__ void narrow_bad_or(unsigned long long bad,
+                                              unsigned long long* __restrict__ word,
+                                              unsigned int lane) {
+    for (int off = 32; off > 0; off >>= 1) bad |= __shfl_down(bad, off, 64);
+    if (lane == 0 && bad != 0) atomicOr(word, bad);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(256) void csp_pack_narrow_probe_kernel(
+    const PackNarrowEntry* __restrict__ segs, unsigned int nseg, unsigned long long total_units,
+    unsigned long long* __restrict__ bad_out) {
+    const unsigned int lane = threadIdx.x & 63;
+    for (unsigned long long unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
+        // last entry whose first unit is <= unit (unit_begin is strictly
+        // increasing: the host leaves zero-element segments out of the table)
+        unsigned int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].unit_begin <= unit) lo = mid; else hi = mid;
+        }
+        const PackNarrowEntry& e = segs[lo];
+        const unsigned long long u = unit - e.unit_begin;
+        const CSP_GLOBAL u32x4* src = (const CSP_GLOBAL u32x4*)e.src;
+        const unsigned long long nsv = e.n;
+        const unsigned long long v0 = u * kPackTileVecs + threadIdx.x;
+        u32x4 v[kPackUnroll];
+        if ((u + 1) * kPackTileVecs <= nsv) {
+#pragma unroll
+            for (int k = 0; k < kPackUnroll; ++k)
+                v[k] = NT ? __builtin_nontemporal_load(&src[v0 + k * 256]) : src[v0 + k * 256];
+        } else {  // the tile that holds the source's end
+            const unsigned int rem = e.rem;
+#pragma unroll
+            for (int k = 0; k < kPackUnroll; ++k) {
+                const unsigned long long sv = v0 + k * 256;
+                v[k] = u32x4{0u, 0u, 0u, 0u};  // a zero is exact for every target
+                if (sv < nsv) v[k] = NT ? __builtin_nontemporal_load(&src[sv]) : src[sv];
+                else if (sv == nsv && rem != 0) v[k] = narrow_load_tail(src + nsv, rem);
+            }
+        }
+        unsigned long long bad = 0;
+        const unsigned int kind = e.what;  // uniform for the workgroup
+#pragma unroll
+        for (int k = 0; k < kPackUnroll; ++k) {
+            if (kind == CSP_KIND_F32) (void)Narrow<CSP_KIND_F32, CSP_KIND_BF16>::apply(v[k], bad);
+            else if (kind == CSP_KIND_F64) (void)Narrow<CSP_KIND_F64, CSP_KIND_F32>::apply(v[k], bad);
+            else if (kind == CSP_KIND_I32) narrow_test_i32(v[k], bad);
+            else narrow_test_i64(v[k], bad);
+        }
+        narrow_bad_or(bad, &bad_out[e.seg], lane);
+    }
+}
+
+// One output tile of a NARROW segment for one wave: the fragment above, with
+// the arena-global word index
+template <int SRC, int DST, typename Strips>
+__device__ __forceinline__ void pack_narrow_tile(const CSP_GLOBAL u32x4* __restrict__ src,
+                                                 size_t nsv, unsigned int rem,
+                                                 u32x4* __restrict__ dst, size_t nov, size_t tile,
+                                                 unsigned int word_base, Strips& strip,
+                                                 unsigned int lane, unsigned int wave,
+                                                 unsigned long long& s0, unsigned long long& t,
+                                                 unsigned long long& bad) {
+    typedef Narrow<SRC, DST> N;
+    constexpr int R = N::R, U = N::kUnroll;
+    typedef typename N::piece_t piece_t;
+    CSP_NARROW_WAVE_STEPS(tile, word_base)
+}
+
+__global__ __launch_bounds__(256) void csp_pack_narrow_checksum_kernel(
+    const PackNarrowEntry* __restrict__ segs, unsigned int nseg, unsigned long long total_units,
+    unsigned char* __restrict__ arena, unsigned long long* __restrict__ out,
+    unsigned long long* __restrict__ bad_out) {
+    __shared__ u32x4 strip[4][2][kNarrowStepVecs];  // the largest trip: two steps per wave
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = threadIdx.x >> 6;
+    unsigned long long s0 = 0, t = 0;
+    for (unsigned long long unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
+        unsigned int lo = 0, hi = nseg;  // as in the probe
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].unit_begin <= unit) lo = mid; else hi = mid;
+        }
+        const PackNarrowEntry& e = segs[lo];
+        const unsigned long long u = unit - e.unit_begin;
+        const unsigned long long dst_off = e.dst_off;
+        // arena-global index of the segment's first word
+        const unsigned int word_base = (unsigned int)(dst_off / 4);
+        u32x4* dst = reinterpret_cast<u32x4*>(arena + dst_off);
+        const unsigned int what = e.what;
+        if (what == kPackNarrowCopyUnit) {
+            const pack_src_t src = (pack_src_t)e.src;
+            const unsigned long long n = e.n;
+            const unsigned int a = (unsigned int)(reinterpret_cast<uintptr_t>(e.src) & 15u);
+            if (a == 0) pack_checksum_tile<16>(src, dst, n, u, word_base, s0, t);
+            else if ((a & 7u) == 0) pack_checksum_tile<8>(src, dst, n, u, word_base, s0, t);
+            else if ((a & 3u) == 0) pack_checksum_tile<4>(src, dst, n, u, word_base, s0, t);
+            else if ((a & 1u) == 0) pack_checksum_tile<2>(src, dst, n, u, word_base, s0, t);
+            else pack_checksum_tile<1>(src, dst, n, u, word_base, s0, t);
+            continue;
+        }
+        __builtin_assume(dst != nullptr);  // the fragment's probe branch is not taken
+        const CSP_GLOBAL u32x4* src = (const CSP_GLOBAL u32x4*)e.src;
+        const unsigned long long nsv = e.n, nov = e.nov;
+        const unsigned int rem = e.rem;
+        unsigned long long bad = 0;
+#define CSP_PACK_NARROW_CASE(S, D)                                                            \
+    case CSP_PACK_NARROW_WHAT(S, D):                                                          \
+        pack_narrow_tile<CSP_KIND_##S, CSP_KIND_##D>(src, nsv, rem, dst, nov, u, word_base,   \
+                                                     strip, lane, wave, s0, t, bad);          \
+        break;
+        switch (what) {  // the host admits kNarrowPairs only
+            CSP_PACK_NARROW_CASE(F32, BF16)
+            CSP_PACK_NARROW_CASE(F64, F32)
+            CSP_PACK_NARROW_CASE(I64, I32)
+            CSP_PACK_NARROW_CASE(I64, I16)
+            CSP_PACK_NARROW_CASE(I64, U8)
+            CSP_PACK_NARROW_CASE(I32, I16)
+            CSP_PACK_NARROW_CASE(I32, U8)
+        }
+#undef CSP_PACK_NARROW_CASE
+        narrow_bad_or(bad, &bad_out[e.seg], lane);
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+// At most 1024 workgroups for both kernels: the cap of the other kernels that
+// carry a checksum.  Carried over, not measured for these.
+static const size_t kPackNarrowGridCapDefault = 1024;
+static size_t g_pack_narrow_grid_cap = kPackNarrowGridCapDefault;
+// The probe's loads: plain, so that the lines are still in the last-level
+// cache when the second kernel reads them; profiles/packed_narrowed_results.md
+// has the comparison with nontemporal ones.
+static const bool kPackNarrowProbeNt = false;
+static bool g_pack_narrow_probe_nt = kPackNarrowProbeNt;
+
+// Tools only: the grid cap of the next csp_pack_narrow_probe_dev and
+// csp_pack_narrow_checksum_dev calls (0 restores the default).  Returns the
+// cap in effect.  With a cap of 1, 2 or 3 every workgroup walks units of
+// every kind in turn.
+extern "C" size_t csp_pack_narrow_checksum_grid_cap(size_t cap) {
+    g_pack_narrow_grid_cap = cap ? std::min(cap, size_t(65536)) : kPackNarrowGridCapDefault;
+    return g_pack_narrow_grid_cap;
+}
+
+// Tools only: 1 makes the next probes load nontemporally, 0 plainly, anything
+// else restores the default.  Returns the value in effect.
+extern "C" int csp_pack_narrow_probe_nt(int on) {
+    g_pack_narrow_probe_nt = on == 1 ? true : on == 0 ? false : kPackNarrowProbeNt;
+    return g_pack_narrow_probe_nt ? 1 : 0;
+}
+
+// narrow_fits() for the callers of the two entry points below: the bit
+// 1 << kind of every target of src_kind that the `bad` word leaves exact.
+extern "C" uint32_t csp_narrow_fits(int src_kind, uint64_t bad) {
+    return narrow_fits(src_kind, bad);
+}
+
+// What both entry points ask of a segment's source: `es` bytes per element
+// (1: a copy), 16-byte alignment where it is narrowed or probed.  false with
+// a message that `who` opens.
+static bool pack_narrow_source(const char* who, const CspPackNarrowSeg& g, unsigned int es,
+                               bool aligned, uint64_t* src_bytes) {
+    if (g.numel > kNarrowMaxSrcBytes / es) {
+        snprintf(g_err, sizeof(g_err), "%s: %llu elements of %u bytes are above the 16 GiB bound",
+                 who, (unsigned long long)g.numel, es);
+        return false;
+    }
+    *src_bytes = g.numel * es;
+    const uintptr_t sa = reinterpret_cast<uintptr_t>(g.src);
+    if (g.numel == 0) return true;
+    if (sa == 0) {
+        snprintf(g_err, sizeof(g_err), "%s has %llu elements at a null pointer", who,
+                 (unsigned long long)g.numel);
+        return false;
+    }
+    if (aligned && sa % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: src %p is not 16-byte aligned", who, g.src);
+        return false;
+    }
+    if (sa + *src_bytes < sa) {
+        snprintf(g_err, sizeof(g_err), "%s: src %p with %llu bytes overflows", who, g.src,
+                 (unsigned long long)*src_bytes);
+        return false;
+    }
+    return true;
+}
+
+// Both launches: the table to the device, sums and `bad` words zeroed, the
+// kernel, everything read back.  `launch(stream, blocks, table, sums, bad)`.
+// sums may be null (the probe).
+template <typename Launch>
+static int pack_narrow_run(const std::vector<PackNarrowEntry>& table, size_t nseg,
+                           uint64_t units, uint64_t* sums, uint64_t* bad_out,
+                           double* kernel_ms, Launch launch) {
+    // two sums and the `bad` words in one grow-only buffer, one grow-only
+    // table per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* dev_words = nullptr;
+    static PackNarrowEntry* dev_table = nullptr;
+    static size_t words_cap = 0, table_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_device != device) {
+        if (dev_words) (void)hipFree(dev_words);
+        if (dev_table) (void)hipFree(dev_table);
+        dev_words = nullptr;
+        dev_table = nullptr;
+        words_cap = table_cap = 0;
+        dev_device = device;
+    }
+    const size_t words = 2 + nseg;
+    if (words_cap < words) {
+        if (dev_words) (void)hipFree(dev_words);
+        dev_words = nullptr;
+        words_cap = 0;
+        size_t cap = 1024;
+        while (cap < words) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_words, cap * sizeof(unsigned long long)));
+        words_cap = cap;
+    }
+    if (table_cap < table.size()) {
+        if (dev_table) (void)hipFree(dev_table);
+        dev_table = nullptr;
+        table_cap = 0;
+        size_t cap = 256;
+        while (cap < table.size()) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_table, cap * sizeof(PackNarrowEntry)));
+        table_cap = cap;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define PACKNARROW_TRY(expr)                                       \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    // `table` outlives the copy: the stream is synchronised below
+    PACKNARROW_TRY(hipMemcpyAsync(dev_table, table.data(),
+                                  table.size() * sizeof(PackNarrowEntry),
+                                  hipMemcpyHostToDevice, s));
+    PACKNARROW_TRY(hipMemsetAsync(dev_words, 0, words * sizeof(unsigned long long), s));
+    const size_t blocks = (size_t)std::min<uint64_t>(units, g_pack_narrow_grid_cap);
+    if (t0) PACKNARROW_TRY(hipEventRecord(t0, s));
+    launch(s, (unsigned int)blocks, dev_table, dev_words, dev_words + 2);
+    PACKNARROW_TRY(hipGetLastError());
+    if (t1) PACKNARROW_TRY(hipEventRecord(t1, s));
+    std::vector<unsigned long long> host(words, 0);
+    PACKNARROW_TRY(hipMemcpyAsync(host.data(), dev_words, words * sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, s));
+    PACKNARROW_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        PACKNARROW_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef PACKNARROW_TRY
+    if (sums) {
+        sums[0] = host[0];
+        sums[1] = host[1];
+    }
+    std::copy(host.begin() + 2, host.end(), bad_out);
+    return done(0);
+}
+
+static unsigned int narrow_src_elem_size(int src_kind) {
+    for (const NarrowPairInfo& p : kNarrowPairs)
+        if (p.src_kind == src_kind) return p.src_es;
+    return 0;
+}
+
+// Test nseg contiguous device segments for exact narrowing in ONE launch:
+// bad_out[k] gets segment k's `bad` word, which csp_narrow_fits(src_kind, .)
+// turns into the targets that give every element back bit for bit.  Nothing
+// else is stored.  A zero-element segment is legal and reads as exact.
+// Returns 0, or -1 with a message that names the segment and nothing launched
+// for a null segs or bad_out, a src_kind that has no target, a null or not
+// 16-byte aligned src, a segment above 16 GiB or 2^31 segments or more; and
+// for a HIP failure.  bad_out is all zero then.  Runs on copy_stream() and
+// synchronises it before returning; sources written on another stream must be
+// complete first.  kernel_ms (optional): the kernel alone, from events around
+// the launch.
+extern "C" int csp_pack_narrow_probe_dev(const CspPackNarrowSeg* segs, size_t nseg,
+                                         uint64_t* bad_out, double* kernel_ms) {
+    const char* fn = "csp_pack_narrow_probe_dev";
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (nseg >= (size_t(1) << 31)) {  // before anything walks the segments
+        snprintf(g_err, sizeof(g_err), "%s: %zu segments are too many", fn, nseg);
+        return -1;
+    }
+    if (nseg != 0 && (segs == nullptr || bad_out == nullptr)) {
+        snprintf(g_err, sizeof(g_err), "%s: null segs or bad_out pointer", fn);
+        return -1;
+    }
+    std::fill(bad_out, bad_out + nseg, uint64_t(0));
+    std::vector<PackNarrowEntry> table;
+    table.reserve(nseg);
+    uint64_t units = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        const CspPackNarrowSeg& g = segs[k];
+        char who[64];
+        snprintf(who, sizeof(who), "%s: segment %zu", fn, k);
+        const unsigned int es = narrow_src_elem_size(g.src_kind);
+        if (es == 0) {
+            snprintf(g_err, sizeof(g_err), "%s: no narrowing from kind %d", who, g.src_kind);
+            return -1;
+        }
+        uint64_t src_bytes = 0;
+        if (!pack_narrow_source(who, g, es, true, &src_bytes)) return -1;
+        if (g.numel == 0) continue;  // owns no unit
+        PackNarrowEntry e = {};
+        e.src = static_cast<const unsigned char*>(g.src);
+        e.n = src_bytes / 16;
+        e.rem = (unsigned int)(src_bytes % 16 / 4);
+        e.what = (unsigned int)g.src_kind;
+        e.seg = (unsigned int)k;
+        e.unit_begin = units;
+        units += (e.n + (e.rem ? 1 : 0) + kPackTileVecs - 1) / kPackTileVecs;
+        table.push_back(e);
+    }
+    if (table.empty()) return 0;
+    const bool nt = g_pack_narrow_probe_nt;
+    const unsigned int count = (unsigned int)table.size();
+    return pack_narrow_run(
+        table, nseg, units, nullptr, bad_out, kernel_ms,
+        [&](hipStream_t s, unsigned int blocks, const PackNarrowEntry* dev_table,
+            unsigned long long*, unsigned long long* bad) {
+            if (nt)
+                hipLaunchKernelGGL(csp_pack_narrow_probe_kernel<true>, dim3(blocks), dim3(256), 0,
+                                   s, dev_table, count, (unsigned long long)units, bad);
+            else
+                hipLaunchKernelGGL(csp_pack_narrow_probe_kernel<false>, dim3(blocks), dim3(256),
+                                   0, s, dev_table, count, (unsigned long long)units, bad);
+        });
+}
+
+// Fill `arena` from nseg contiguous device segments, each either copied byte
+// for byte (dst_kind CSP_PACK_NARROW_COPY: numel bytes at any alignment) or
+// narrowed from src_kind to dst_kind (a pair of csp_narrow_checksum_dev), and
+// put csp_checksum_dev(arena, arena_bytes) into sums[2], from ONE launch.
+// The layout is csp_pack_dev's over the bytes each segment occupies in the
+// arena (numel bytes, or numel target elements): segment k at dst_off[k], each
+// at the next multiple of 16 after the one before, the padding zero,
+// arena_bytes their total.  bad_out[k] gets the `bad` word of a narrowed
+// segment, from the pass that wrote it: where csp_narrow_fits(src_kind,
+// bad_out[k]) lacks the bit of dst_kind the segment's bytes mean nothing and
+// the caller must not send the arena.  A copy's word is 0.  A zero-element
+// segment is legal and owns no unit.  Returns 0, or -1 with a message that
+// names the segment and nothing launched for: a null segs, sums, bad_out or
+// arena; a pair that is not served; a narrowed segment whose src is not
+// 16-byte aligned; a null src with elements; a dst_off that is not a multiple
+// of 16, or not where the layout rule puts it (out of order, overlapping, a
+// gap); a segment that ends past arena_bytes; an arena_bytes that is not a
+// multiple of 16, is above 16 GiB or is not the segments' total; an arena that
+// is not 16-byte aligned; a source that overlaps the arena; 2^31 segments or
+// more; and for a HIP failure.  Runs on copy_stream(), so it is ordered before
+// a csp_d2h_stream_fd of the arena, and synchronises that stream before
+// returning; sources written on another stream must be complete first.
+// kernel_ms (optional): the kernel alone, from events around the launch.
+extern "C" int csp_pack_narrow_checksum_dev(const CspPackNarrowSeg* segs, size_t nseg,
+                                            void* arena, size_t arena_bytes, uint64_t sums[2],
+                                            uint64_t* bad_out, double* kernel_ms) {
+    const char* fn = "csp_pack_narrow_checksum_dev";
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (sums == nullptr) {
+        snprintf(g_err, sizeof(g_err), "%s: null sums pointer", fn);
+        return -1;
+    }
+    sums[0] = sums[1] = 0;
+    if (nseg >= (size_t(1) << 31)) {  // before anything walks the segments
+        snprintf(g_err, sizeof(g_err), "%s: %zu segments are too many", fn, nseg);
+        return -1;
+    }
+    if (nseg != 0 && (segs == nullptr || bad_out == nullptr)) {
+        snprintf(g_err, sizeof(g_err), "%s: null segs or bad_out pointer", fn);
+        return -1;
+    }
+    std::fill(bad_out, bad_out + nseg, uint64_t(0));
+    if (arena_bytes % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: arena_bytes %zu is not a multiple of 16", fn,
+                 arena_bytes);
+        return -1;
+    }
+    if ((uint64_t)arena_bytes > kPackChecksumMaxBytes) {
+        snprintf(g_err, sizeof(g_err), "%s: arena_bytes %zu is above 16 GiB", fn, arena_bytes);
+        return -1;
+    }
+    const uintptr_t a = reinterpret_cast<uintptr_t>(arena);
+    if (a + arena_bytes < a) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at arena %p overflow", fn, arena_bytes,
+                 arena);
+        return -1;
+    }
+    if (a % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: arena pointer %p is not 16-byte aligned", fn, arena);
+        return -1;
+    }
+    if (arena == nullptr && arena_bytes != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: null arena for %zu bytes", fn, arena_bytes);
+        return -1;
+    }
+    std::vector<PackNarrowEntry> table;
+    table.reserve(nseg);
+    uint64_t expect = 0, units = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        const CspPackNarrowSeg& g = segs[k];
+        char who[64];
+        snprintf(who, sizeof(who), "%s: segment %zu", fn, k);
+        const bool copy = g.dst_kind == CSP_PACK_NARROW_COPY;
+        const NarrowPairInfo* pair = nullptr;
+        for (const NarrowPairInfo& p : kNarrowPairs)
+            if (!copy && p.src_kind == g.src_kind && p.dst_kind == g.dst_kind) pair = &p;
+        if (!copy && pair == nullptr) {
+            snprintf(g_err, sizeof(g_err), "%s: no narrowing from kind %d to kind %d", who,
+                     g.src_kind, g.dst_kind);
+            return -1;
+        }
+        uint64_t src_bytes = 0;
+        if (!pack_narrow_source(who, g, copy ? 1u : pair->src_es, !copy, &src_bytes)) return -1;
+        if (g.dst_off % 16 != 0) {
+            snprintf(g_err, sizeof(g_err), "%s: dst_off %llu is not a multiple of 16", who,
+                     (unsigned long long)g.dst_off);
+            return -1;
+        }
+        if (g.dst_off != expect) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: dst_off is %llu, the layout rule gives %llu (segments in order, "
+                     "neither overlapping nor apart)",
+                     who, (unsigned long long)g.dst_off, (unsigned long long)expect);
+            return -1;
+        }
+        const uint64_t out_bytes = copy ? src_bytes : g.numel * pair->dst_es;
+        const uint64_t rounded = (out_bytes + 15) & ~uint64_t(15);
+        if (expect + rounded > (uint64_t)arena_bytes) {
+            snprintf(g_err, sizeof(g_err), "%s ends at %llu, past arena_bytes %zu", who,
+                     (unsigned long long)(expect + rounded), arena_bytes);
+            return -1;
+        }
+        expect += rounded;
+        if (g.numel == 0) continue;  // owns no unit
+        const uintptr_t sa = reinterpret_cast<uintptr_t>(g.src);
+        if (sa < a + arena_bytes && a < sa + src_bytes) {
+            snprintf(g_err, sizeof(g_err), "%s: %llu source bytes at %p overlap the arena at %p",
+                     who, (unsigned long long)src_bytes, g.src, arena);
+            return -1;
+        }
+        PackNarrowEntry e = {};
+        e.src = static_cast<const unsigned char*>(g.src);
+        e.dst_off = g.dst_off;
+        e.nov = rounded / 16;
+        e.seg = (unsigned int)k;
+        e.unit_begin = units;
+        if (copy) {
+            e.what = kPackNarrowCopyUnit;
+            e.n = src_bytes;
+        } else {
+            e.what = (unsigned int)(g.src_kind * 8 + g.dst_kind);
+            e.n = src_bytes / 16;
+            e.rem = (unsigned int)(src_bytes % 16 / 4);
+        }
+        units += (rounded + kPackTileBytes - 1) / kPackTileBytes;
+        table.push_back(e);
+    }
+    if (expect != (uint64_t)arena_bytes) {
+        snprintf(g_err, sizeof(g_err), "%s: arena_bytes is %zu, the segments need %llu", fn,
+                 arena_bytes, (unsigned long long)expect);
+        return -1;
+    }
+    if (table.empty()) return 0;
+    const unsigned int count = (unsigned int)table.size();
+    return pack_narrow_run(
+        table, nseg, units, sums, bad_out, kernel_ms,
+        [&](hipStream_t s, unsigned int blocks, const PackNarrowEntry* dev_table,
+            unsigned long long* acc, unsigned long long* bad) {
+            hipLaunchKernelGGL(csp_pack_narrow_checksum_kernel, dim3(blocks), dim3(256), 0, s,
+                               dev_table, count, (unsigned long long)units,
+                               static_cast<unsigned char*>(arena), acc, bad);
+        });
 }
 
 // ---------------------------------------------------------------------------

@@ -135,8 +135,20 @@ Protocol (all frames: 8-byte big-endian length + payload):
              meta["staging"] counts "narrowed", "narrow_saved_bytes" and
              "narrow_ms" (the calls and the buffer, the inexact ones too),
              and a tensor that is not exact or is refused travels whole
-             with the reason in "narrow_fallback".  The packed
-             arena likewise: its non-contiguous tensors that
+             with the reason in "narrow_fallback".  With
+             pack_tensor_results as well, a packed arena that is not retained
+             and holds no strided tensor is narrowed too: ONE
+             csp_pack_narrow_probe_dev call tests its contiguous, 16-byte
+             aligned float32, float64, int32 and int64 tensors, and ONE
+             csp_pack_narrow_checksum_dev call fills an arena laid out at the
+             narrow sizes (each rounded up to 16), narrowed tensors and plain
+             copies together, sums it and confirms every verdict; a
+             narrowed tensor's "packed" entry gains "wire", its "offset" and
+             "nbytes" are those of the narrow bytes, "nbytes" and "sum" of the
+             buffer are the narrow arena's, and the same three counters count.
+             When nothing narrows or the calls are refused the arena travels
+             wide, as without the option.  As for gather_tensor_results, the
+             packed arena likewise: its non-contiguous tensors that
              csp_gather_supported serves stay as they are and ONE
              csp_pack_gather_checksum_dev call fills and sums the arena from
              contiguous and strided tensors together; the others (more than 4
@@ -410,6 +422,26 @@ def _load_gpu_lib():
             ctypes.POINTER(ctypes.c_uint32),
             ctypes.POINTER(ctypes.c_float),
         ]
+    if NARROW_RESULTS and PACK_RESULTS and _has_pack_narrow(lib):
+        lib.csp_pack_narrow_probe_dev.restype = ctypes.c_int
+        lib.csp_pack_narrow_probe_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_double),
+        ]
+        lib.csp_pack_narrow_checksum_dev.restype = ctypes.c_int
+        lib.csp_pack_narrow_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_double),
+        ]
+        lib.csp_narrow_fits.restype = ctypes.c_uint32
+        lib.csp_narrow_fits.argtypes = [ctypes.c_int, ctypes.c_uint64]
     if hasattr(lib, "csp_widen_checksum_dev"):
         lib.csp_widen_checksum_dev.restype = ctypes.c_int
         lib.csp_widen_checksum_dev.argtypes = [
@@ -678,6 +710,108 @@ def _narrow(lib, t, stats):
     return flat, wire, name, sums
 
 
+def _has_pack_narrow(lib):
+    """Whether the library has all that _pack_narrow calls."""
+    return all(
+        hasattr(lib, name) for name in
+        ("csp_pack_narrow_probe_dev", "csp_pack_narrow_checksum_dev", "csp_narrow_fits")
+    )
+
+
+def _pack_narrow(lib, tensors, srcs, sizes, stats):
+    """The packed arena with every tensor at the narrowest width that is
+    exact: (arena, total, offsets, bytes per segment, wire dtype name or None
+    per segment, [s0, s1] of the arena), or None when nothing narrows or
+    anything is refused or fails, the reason then in stats["narrow_fallback"]:
+    a narrowing never fails a task.  ``srcs`` are all contiguous.  Candidates
+    are the tensors that were contiguous as they came, have a dtype of
+    NARROW_TARGETS and a 16-byte aligned pointer; ONE csp_pack_narrow_probe_dev
+    call yields their verdicts, the tightest fitting target of each is picked
+    as _narrow picks it, and ONE csp_pack_narrow_checksum_dev call fills and
+    sums the arena, narrowed segments and plain copies together, and confirms
+    every verdict from the pass that wrote the bytes.  The caller has
+    synchronised the null stream."""
+    import ctypes
+
+    import torch
+
+    def check(rc, what):
+        if rc != 0:
+            raise RuntimeError(
+                "%s failed (rc=%d): %s"
+                % (what, rc, lib.csp_last_error().decode(errors="replace"))
+            )
+
+    def table(rows):
+        # CspPackNarrowSeg as 4 u64: src, numel, src_kind | dst_kind << 32, dst_off
+        flat = (ctypes.c_uint64 * (4 * len(rows)))()
+        for k, (ptr, numel, src_kind, dst_kind, off) in enumerate(rows):
+            flat[4 * k : 4 * k + 4] = [ptr, numel, src_kind | (dst_kind & 0xFFFFFFFF) << 32, off]
+        return flat
+
+    names = [str(t.dtype).replace("torch.", "") for t in tensors]
+    cand = [
+        k for k, (t, s, n) in enumerate(zip(tensors, srcs, sizes))
+        if n and s is t and names[k] in NARROW_TARGETS and s.data_ptr() % 16 == 0
+    ]
+    if not cand:
+        return None
+    t0 = time.monotonic()
+    try:
+        bad = (ctypes.c_uint64 * len(cand))()
+        check(
+            lib.csp_pack_narrow_probe_dev(
+                table([(srcs[k].data_ptr(), srcs[k].numel(), NARROW_KINDS[names[k]], 0, 0)
+                       for k in cand]),
+                len(cand), bad, None,
+            ),
+            "csp_pack_narrow_probe_dev",
+        )
+        picked = {}  # segment -> (target name, kind, element size)
+        for j, k in enumerate(cand):
+            fits = lib.csp_narrow_fits(NARROW_KINDS[names[k]], bad[j])
+            target = [x for x in NARROW_TARGETS[names[k]] if fits >> x[1] & 1][:1]
+            if target:
+                picked[k] = target[0]
+        if not picked:
+            raise ValueError("no packed tensor is exact at a narrower width")
+        wire_sizes = [
+            srcs[k].numel() * picked[k][2] if k in picked else n for k, n in enumerate(sizes)
+        ]
+        offsets = []
+        total = 0
+        for n in wire_sizes:
+            offsets.append(total)
+            total += (n + 15) // 16 * 16
+        arena = torch.empty(total, dtype=torch.uint8, device="cuda")
+        rows = [
+            (s.data_ptr(), s.numel(), NARROW_KINDS[names[k]], picked[k][1], off)
+            if k in picked else (s.data_ptr() if n else 0, n, 0, -1, off)
+            for k, (s, n, off) in enumerate(zip(srcs, sizes, offsets))
+        ]
+        sums = (ctypes.c_uint64 * 2)()
+        bad = (ctypes.c_uint64 * len(rows))()
+        check(
+            lib.csp_pack_narrow_checksum_dev(
+                table(rows), len(rows), ctypes.c_void_p(arena.data_ptr()), total, sums, bad, None
+            ),
+            "csp_pack_narrow_checksum_dev",
+        )
+        for k, (_name, kind, _size) in picked.items():
+            if not lib.csp_narrow_fits(NARROW_KINDS[names[k]], bad[k]) >> kind & 1:
+                raise ValueError("packed tensor %d changed between the probe and the pack" % k)
+    except Exception as e:  # noqa: BLE001
+        stats.setdefault("narrow_fallback", repr(e)[:500])  # an earlier reason stays
+        return None
+    finally:
+        stats["narrow_ms"] = round(
+            stats.get("narrow_ms", 0.0) + (time.monotonic() - t0) * 1000, 3)
+    stats["narrowed"] = stats.get("narrowed", 0) + len(picked)
+    stats["narrow_saved_bytes"] = stats.get("narrow_saved_bytes", 0) + sum(sizes) - sum(wire_sizes)
+    wires = [picked[k][0] if k in picked else None for k in range(len(srcs))]
+    return arena, total, offsets, wire_sizes, wires, [int(sums[0]), int(sums[1])]
+
+
 def _packs_strided(lib, t):
     """Whether the non-contiguous CUDA tensor ``t`` stays as it is in the
     packed arena, as a strided segment of csp_pack_gather_checksum_dev."""
@@ -883,7 +1017,14 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
     stays as it is, and when there is one, ONE csp_pack_gather_checksum_dev
     call fills and sums the arena, retained or not; its refusal goes to
     stats["gather_fallback"] and the calls above run with contiguous() for
-    all."""
+    all.
+
+    With NARROW_RESULTS, an arena that is not retained and has no strided
+    segment is allocated at its narrow size and filled by _pack_narrow: the
+    "packed" entry of a narrowed tensor gains "wire", its "offset" and
+    "nbytes" describe the narrow bytes, and "sum" is over the narrow arena.
+    When nothing narrows or anything is refused, the calls above run
+    unchanged."""
     import ctypes
 
     import torch
@@ -911,12 +1052,19 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
         ptrs = [(t.data_ptr() or None) if n else None for t, n in zip(srcs, sizes)]
         segments = list(zip(srcs, offsets, sizes, strided)) if any(strided) else None
         kept = None
+        narrowed = None
+        wire_sizes, wires = sizes, [None] * count
+        if NARROW_RESULTS and retain is None and segments is None and _has_pack_narrow(lib):
+            # a retained master keeps its full bytes to serve as an argument
+            narrowed = _pack_narrow(lib, tensors, srcs, sizes, stats)
         if retain is not None:
             kept = _retain_buffer(
                 lib, retain, len(buffers), segments or ptrs, None if segments else offsets,
                 sizes, total, total, stats, keep=total >= max(1, RETAIN_MIN_BYTES),
             )
-        if kept is not None:
+        if narrowed is not None:
+            arena, total, offsets, wire_sizes, wires, sums = narrowed
+        elif kept is not None:
             arena, sums, name = kept
         else:
             arena = torch.empty(total, dtype=torch.uint8, device="cuda")
@@ -928,7 +1076,7 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
                     stats["gather_fallback"] = repr(e)[:500]
             if sums is None and segments is not None:
                 srcs, ptrs = _flat_sources(segments)
-        if kept is None and sums is None:
+        if narrowed is None and kept is None and sums is None:
             rc = lib.csp_pack_dev(
                 (ctypes.c_void_p * count)(*ptrs), (ctypes.c_uint64 * count)(*offsets),
                 (ctypes.c_uint64 * count)(*sizes), count,
@@ -958,9 +1106,12 @@ def _pack_small_cuda(lib, result, stats, buffers, buffer_meta, retain=None):
     buffers.append((_DeferredCuda(lib, arena.data_ptr(), total), arena))
     buffer_meta.append({
         "packed": [
-            {"dtype": str(t.dtype).replace("torch.", ""), "shape": list(t.shape),
-             "offset": off, "nbytes": n}
-            for t, off, n in zip(tensors, offsets, sizes)
+            dict(
+                {"dtype": str(t.dtype).replace("torch.", ""), "shape": list(t.shape),
+                 "offset": off, "nbytes": n},
+                **({"wire": wire} if wire else {})
+            )
+            for t, off, n, wire in zip(tensors, offsets, wire_sizes, wires)
         ],
         "nbytes": total,
         "sum": [int(sums[0]), int(sums[1])],
@@ -1155,7 +1306,7 @@ def _delta_results(lib, masters, buffers, buffer_meta, stats):
     for i, (view, _keep) in enumerate(buffers):
         if not isinstance(view, _DeferredCuda) or view.nbytes < floor:
             continue
-        if "wire" in buffer_meta[i]:
+        if "wire" in buffer_meta[i] or any("wire" in e for e in buffer_meta[i].get("packed", ())):
             continue  # narrowed: these are not the result's own bytes
         pair = next(
             (k for k, m in enumerate(masters) if k not in used and m[2] == view.nbytes),

@@ -710,7 +710,9 @@ def _reconstruct(result, buffer_meta, buffers, rebuilt_out=None):
     ``offset`` into the received buffer.  All tensors of one packed buffer
     share that buffer, which stays alive as long as any of them does (so one
     small survivor keeps the whole frame in memory; ``clone()`` it to let
-    go).  Their byte ranges do not overlap.  A marker met twice gives the
+    go).  Their byte ranges do not overlap.  An entry with ``"wire"`` holds
+    its elements at that narrower dtype: it is widened by
+    :func:`widen_result` and owns new memory.  A marker met twice gives the
     same tensor object, as the worker had it."""
     import torch
 
@@ -732,6 +734,13 @@ def _reconstruct(result, buffer_meta, buffers, rebuilt_out=None):
                 count *= int(dim)
             if count == 0:
                 t = torch.empty(info["shape"], dtype=dtype)
+            elif "wire" in info:
+                # narrowed inside the arena (narrow_tensor_results with
+                # pack_tensor_results): widened, it owns new memory
+                start = int(info["offset"])
+                t = widen_result(
+                    memoryview(shared(i)).cast("B")[start : start + int(info["nbytes"])], info
+                )
             else:
                 t = torch.frombuffer(
                     shared(i), dtype=dtype, count=count, offset=int(info["offset"])
