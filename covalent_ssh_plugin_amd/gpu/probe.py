@@ -97,6 +97,21 @@ class PackNarrowSeg(ctypes.Structure):
     ]
 
 
+class UnpackWidenSeg(ctypes.Structure):
+    """``CspUnpackWidenSeg``: one segment of ``csp_unpack_widen_checksum_dev``.
+    ``narrow_kind == -1`` is a copy of ``count`` bytes; otherwise ``count``
+    elements widened from ``narrow_kind`` to ``wide_kind``."""
+
+    _fields_ = [
+        ("dst", ctypes.c_void_p),
+        ("src_off", ctypes.c_uint64),
+        ("dst_off", ctypes.c_uint64),
+        ("count", ctypes.c_uint64),
+        ("narrow_kind", ctypes.c_int32),
+        ("wide_kind", ctypes.c_int32),
+    ]
+
+
 def local_gpu_lib_path() -> str:
     """Path of the built in-tree library, or '' if not built."""
     candidate = Path(__file__).resolve().parent.parent / "ops" / _LIB_NAME
@@ -320,6 +335,19 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_widen_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_widen_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_unpack_widen_checksum_dev.restype = ctypes.c_int
+    lib.csp_unpack_widen_checksum_dev.argtypes = [
+        ctypes.POINTER(UnpackWidenSeg),
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.csp_unpack_widen_checksum_grid_cap.restype = ctypes.c_size_t
+    lib.csp_unpack_widen_checksum_grid_cap.argtypes = [ctypes.c_size_t]
     lib.csp_gather_checksum_dev.restype = ctypes.c_int
     lib.csp_gather_checksum_dev.argtypes = [
         ctypes.c_void_p,
@@ -1003,6 +1031,68 @@ def widen_checksum_grid_cap(cap: int = 0) -> int:
     """Tools only: set the grid cap of :func:`widen_checksum_device` (0
     restores the shipped default).  Returns the cap in effect."""
     return int(load().csp_widen_checksum_grid_cap(int(cap)))
+
+
+def unpack_widen_layout(segments):
+    """``(narrow offsets, narrow total, wide offsets, wide total)`` of an
+    argument arena of ``(count, narrow, wide)`` segments: :func:`pack_layout`
+    over the bytes each has on the wire and over its full-width bytes.
+    ``narrow == ""`` is a copy of ``count`` bytes; otherwise ``count`` elements
+    travel as ``narrow`` and are ``wide`` on the device."""
+    src_off, narrow_total = pack_layout(
+        [n * NARROW_ELEM_SIZE[narrow] if narrow else n for n, narrow, _wide in segments]
+    )
+    dst_off, wide_total = pack_layout(
+        [n * NARROW_ELEM_SIZE[wide] if narrow else n for n, narrow, wide in segments]
+    )
+    return src_off, narrow_total, dst_off, wide_total
+
+
+def unpack_widen_checksum_device(
+    segments, narrow_ptr: int, narrow_bytes: int, master_ptr: int, wide_bytes: int
+) -> dict:
+    """Unpack the narrow device arena at ``narrow_ptr`` into ``segments``,
+    ``(dst_ptr, src_off, dst_off, count, narrow, wide)`` each, at full width
+    and checksum the WIDE arena in ONE kernel launch (``pack_tensor_args``
+    with ``narrow_tensor_args``).  ``narrow == ""`` copies ``count`` bytes;
+    otherwise ``count`` ``narrow`` elements are widened to ``wide`` (a pair of
+    :func:`widen_checksum_device`).  Offsets and totals follow
+    :func:`unpack_widen_layout`.  With ``master_ptr`` set every segment is also
+    written there at ``dst_off``, the padding after a widened segment zero:
+    afterwards it is the wide arena.  Returns ``{"sum", "kernel_ms"}``;
+    ``sum`` is :func:`checksum_device` of the wide arena.  A layout violation,
+    an unserved pair, a null or misaligned pointer, ``wide_bytes`` above 4 GiB
+    or an overlap among the narrow arena, the master and a destination raises
+    ``GpuLibError`` naming the segment and launches nothing.  Runs on the
+    library's copy stream; work on the buffers on another stream must be
+    complete first."""
+    lib = load()
+    n = len(segments)
+    table = (UnpackWidenSeg * max(1, n))()
+    for row, (dst, src_off, dst_off, count, narrow, wide) in zip(table, segments):
+        row.dst = int(dst) or None
+        row.src_off = int(src_off)
+        row.dst_off = int(dst_off)
+        row.count = int(count)
+        row.narrow_kind = NARROW_KINDS.get(narrow, -2) if narrow else -1
+        row.wide_kind = NARROW_KINDS.get(wide, -2) if narrow else 0
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    _check(
+        lib,
+        lib.csp_unpack_widen_checksum_dev(
+            table, n, ctypes.c_void_p(narrow_ptr or None), narrow_bytes,
+            ctypes.c_void_p(master_ptr or None), wide_bytes, out, ctypes.byref(kernel_ms),
+        ),
+        "csp_unpack_widen_checksum_dev",
+    )
+    return {"sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
+
+
+def unpack_widen_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`unpack_widen_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_unpack_widen_checksum_grid_cap(int(cap)))
 
 
 GATHER_PATHS = {0: "none", 1: "direct", 2: "direct16", 3: "transpose", 5: "slab"}

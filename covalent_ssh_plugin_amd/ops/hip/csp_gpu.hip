@@ -5462,6 +5462,70 @@ __device__ __forceinline__ void widen_store(u32x4* __restrict__ dst, size_t wv, 
     }
 }
 
+// the same for a destination that came out of a table in memory (see CSP_GLOBAL)
+__device__ __forceinline__ void widen_store(CSP_GLOBAL u32x4* __restrict__ dst, size_t wv,
+                                            size_t nwv, unsigned int rem, u32x4 o) {
+    if (wv < nwv) {
+        __builtin_nontemporal_store(o, &dst[wv]);
+    } else {
+        CSP_GLOBAL unsigned int* w = reinterpret_cast<CSP_GLOBAL unsigned int*>(dst + nwv);
+#pragma unroll
+        for (unsigned int j = 0; j < 3; ++j)
+            if (j < rem) w[j] = o[j];
+    }
+}
+
+// One wave's four steps of narrow tile TILE, in trips of U steps: the body both
+// widening kernels share, written once.  A textual fragment, not a function,
+// for the reason CSP_NARROW_WAVE_STEPS gives: expanded inside
+// csp_widen_checksum_kernel the compiler sees that kernel's own loop and keeps
+// its register allocation (profiles/packed_narrowed_args.md has the figures
+// before and after).  The scope supplies W = Widen<NARROW, WIDE>, R, U and
+// piece_t; src, nnv (narrow vectors, the last one possibly with pad bytes), dst,
+// nwv (wide vectors wholly below the element count), rem (4-byte words of the
+// partial one after them); strip, LDS of [4 waves][U or more][64 vectors];
+// lane, wave; s0, t.  WORD_BASE: the index of dst's first word in what is
+// summed (0 for a buffer of its own, the wide offset / 4 inside an arena).
+// SECOND: a statement that stores wide vector `o` (the words a partial one
+// lacks already zero) at index `wv` to a second destination.  step0 depends on
+// the tile, the wave and the trip alone: every branch on it is wave-uniform,
+// and all 64 lanes reach the strip together.
+#define CSP_WIDEN_WAVE_STEPS(TILE, WORD_BASE, SECOND)                                           \
+    for (int j = 0; j < kNarrowStepsPerWave; j += U) {                                          \
+        const size_t step0 = ((TILE) * 4 + wave) * kNarrowStepsPerWave + j;                     \
+        if (step0 * kNarrowStepVecs >= nnv) break; /* the last tile's unused steps */           \
+        const size_t nv0 = step0 * kNarrowStepVecs + lane;                                      \
+        u32x4 v[U];                                                                             \
+        if ((step0 + U) * kNarrowStepVecs <= nnv) {                                             \
+            _Pragma("unroll") for (int u = 0; u < U; ++u)                                       \
+                v[u] = __builtin_nontemporal_load(&src[nv0 + u * kNarrowStepVecs]);             \
+        } else { /* the trip that holds the input's end */                                      \
+            _Pragma("unroll") for (int u = 0; u < U; ++u) {                                     \
+                const size_t nv = nv0 + u * kNarrowStepVecs;                                    \
+                v[u] = u32x4{0u, 0u, 0u, 0u};                                                   \
+                if (nv < nnv) v[u] = __builtin_nontemporal_load(&src[nv]);                      \
+            }                                                                                   \
+        }                                                                                       \
+        _Pragma("unroll") for (int u = 0; u < U; ++u) strip[wave][u][lane] = v[u];              \
+        narrow_strip_sync();                                                                    \
+        _Pragma("unroll") for (int u = 0; u < U; ++u) {                                         \
+            const piece_t* pieces = reinterpret_cast<const piece_t*>(&strip[wave][u][0]);       \
+            _Pragma("unroll") for (int k = 0; k < R; ++k) {                                     \
+                const size_t wv = ((step0 + u) * R + k) * kNarrowStepVecs + lane;               \
+                u32x4 o = W::apply(pieces[k * kNarrowStepVecs + lane]);                         \
+                if (wv > nwv || (wv == nwv && rem == 0)) continue;                              \
+                if (wv == nwv) { /* the partial vector: its missing words are zero */           \
+                    _Pragma("unroll") for (unsigned int q = 1; q < 4; ++q)                      \
+                        if (q >= rem) o[q] = 0u;                                                \
+                }                                                                               \
+                checksum_add(s0, t, o, (WORD_BASE) + (unsigned int)(wv * 4));                   \
+                widen_store(dst, wv, nwv, rem, o);                                              \
+                SECOND                                                                          \
+            }                                                                                   \
+        }                                                                                       \
+        narrow_strip_sync(); /* the next trip overwrites the strip */                           \
+    }
+
 // nnv: narrow vectors, the last one possibly with pad bytes; nwv: wide
 // vectors wholly below numel; rem: 4-byte words of the partial one after them
 template <int NARROW, int WIDE>
@@ -5478,48 +5542,7 @@ __global__ __launch_bounds__(256) void csp_widen_checksum_kernel(
     const unsigned int wave = threadIdx.x >> 6;
     unsigned long long s0 = 0, t = 0;
     for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        // step0 depends on the tile, the wave and j alone: every branch on it
-        // is wave-uniform, and all 64 lanes reach the strip together
-        for (int j = 0; j < kNarrowStepsPerWave; j += U) {
-            const size_t step0 = (tile * 4 + wave) * kNarrowStepsPerWave + j;
-            if (step0 * kNarrowStepVecs >= nnv) break;  // the last tile's unused steps
-            const size_t nv0 = step0 * kNarrowStepVecs + lane;
-            u32x4 v[U];
-            if ((step0 + U) * kNarrowStepVecs <= nnv) {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    v[u] = __builtin_nontemporal_load(&src[nv0 + u * kNarrowStepVecs]);
-            } else {  // the trip that holds the input's end
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const size_t nv = nv0 + u * kNarrowStepVecs;
-                    v[u] = u32x4{0u, 0u, 0u, 0u};
-                    if (nv < nnv) v[u] = __builtin_nontemporal_load(&src[nv]);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) strip[wave][u][lane] = v[u];
-            narrow_strip_sync();
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const piece_t* pieces = reinterpret_cast<const piece_t*>(&strip[wave][u][0]);
-#pragma unroll
-                for (int k = 0; k < R; ++k) {
-                    const size_t wv = ((step0 + u) * R + k) * kNarrowStepVecs + lane;
-                    u32x4 o = W::apply(pieces[k * kNarrowStepVecs + lane]);
-                    if (wv > nwv || (wv == nwv && rem == 0)) continue;
-                    if (wv == nwv) {  // the partial vector: its missing words are zero
-#pragma unroll
-                        for (unsigned int q = 1; q < 4; ++q)
-                            if (q >= rem) o[q] = 0u;
-                    }
-                    checksum_add(s0, t, o, (unsigned int)(wv * 4));
-                    widen_store(dst, wv, nwv, rem, o);
-                    if (dst2 != nullptr) widen_store(dst2, wv, nwv, rem, o);
-                }
-            }
-            narrow_strip_sync();  // the next trip overwrites the strip
-        }
+        CSP_WIDEN_WAVE_STEPS(tile, 0u, if (dst2 != nullptr) widen_store(dst2, wv, nwv, rem, o);)
     }
     unsigned long long s1 = t + s0;
 
@@ -5693,6 +5716,466 @@ extern "C" int csp_widen_checksum_dev(const void* src, size_t numel, int narrow_
 #undef WIDEN_TRY
     sums[0] = host[0];
     sums[1] = host[1];
+    return done(0);
+}
+
+// ---------------------------------------------------------------------------
+// Widening inside the packed argument arena: unpack, widen and sum in one launch
+// ---------------------------------------------------------------------------
+//
+// The small tensor arguments of one electron share one frame
+// (pack_tensor_args).  With narrow_tensor_args the dispatcher narrows every
+// segment that narrow_arg's rules allow, so the frame is a NARROW arena: the
+// segments in order at the pack layout of the bytes they have on the wire.
+// csp_unpack_checksum_kernel moves 16-byte vectors and cannot change width;
+// csp_widen_checksum_kernel serves one tensor per launch and knows neither
+// segments nor arena-global word indices nor a master.  This kernel reads the
+// narrow arena once and, in that one pass,
+//
+//   - writes every segment at full width into the electron's private tensor,
+//   - with `master` set (the arena is being cached) writes every segment into
+//     the master too, which has the WIDE pack layout: what hits, patches,
+//     rebases and result deltas read later is the arena they read today,
+//   - sums the wide arena: the result is csp_checksum_dev(wide arena), the sum
+//     the dispatcher announces, with word weights from the wide offset.
+//     Widening is injective, so a damaged narrow byte changes that sum.
+//
+// Work list: one entry per non-empty segment; a unit is 16 KiB of the
+// segment's bytes in the NARROW arena (a copy: 16 KiB of itself; a widened
+// segment: one tile of csp_widen_checksum_kernel, 32 to 128 KiB of output).
+// A workgroup takes unit += gridDim.x, finds the entry by the pack kernels'
+// wave-uniform binary search over the host-built prefix and branches
+// workgroup-uniformly on the pair:
+//
+//   - COPY is the unpack kernel's tile: four plain 16-byte loads per lane
+//     before the first use, nontemporal stores to dst, unpack_store_tail for
+//     the last nbytes % 16 bytes.  With a master every vector is also stored
+//     there whole by a plain aligned store (the next hit reads it), the
+//     padding as it arrived, as the patch kernel does;
+//   - WIDEN is CSP_WIDEN_WAVE_STEPS, the trip csp_widen_checksum_kernel runs:
+//     a wave owns 4 steps of 64 narrow vectors, all nontemporal loads of a trip
+//     issued before the first use, one b128 per lane into a wave-private LDS
+//     strip, R reads of 16 / R bytes consecutive across the lanes, Widen::apply,
+//     and every store instruction of a wave writes 1 KiB contiguously to dst
+//     (nontemporal) and, through a branch that is uniform for the grid, to the
+//     master (plain).  The narrow pad bytes are neither stored nor summed.  The
+//     last partial wide vector goes to dst word by word and to the master
+//     whole, its missing words zero: the master's padding is zero.
+//
+// One strip array serves all seven pairs: 4 waves x 4 steps x 1 KiB = 16 KiB
+// (the trip of the R = 2 pairs).  Strips are wave-private, so no unit needs a
+// workgroup barrier; a wave-scope fence orders its LDS writes and reads.  With
+// the 64 bytes of the final reduction a workgroup holds 16448 bytes of LDS:
+// nine fit the 160 KiB of a CU, more than the eight workgroups of four waves
+// that its 32 wave slots hold, so LDS does not limit occupancy.  The registers
+// do: 68 VGPRs leave seven waves per SIMD, SEVEN workgroups per CU (the
+// compiler's figures are in profiles/packed_narrowed_args.md).  The per-lane u64 s0/t
+// accumulators are carried across units of both kinds and end in shuffles, LDS
+// and one atomic pair per workgroup.  At most 1024 workgroups: the cap of the
+// other checksum-carrying kernels, carried over, not measured for this one.
+// Nothing is multiplied, so there is no MFMA here.
+#define CSP_UNPACK_WIDEN_COPY (-1)  // narrow_kind of a segment that is only copied
+
+// One segment of csp_unpack_widen_checksum_dev.  Plain C, fixed layout, 40
+// bytes.  count: bytes of a copy, elements of a widened segment.
+struct CspUnpackWidenSeg {
+    void* dst;
+    uint64_t src_off;     // in the narrow arena
+    uint64_t dst_off;     // in the wide arena (the master's layout)
+    uint64_t count;
+    int32_t narrow_kind;  // CSP_KIND_BF16, F32, I32, I16 or U8, or CSP_UNPACK_WIDEN_COPY
+    int32_t wide_kind;    // the tensor's own kind; not looked at for a copy
+};
+static_assert(sizeof(CspUnpackWidenSeg) == 40, "the layout the bindings declare");
+
+// n: a copy: bytes; widened: narrow vectors, the last one possibly with pad bytes
+struct UnpackWidenEntry {
+    unsigned char* dst;
+    unsigned long long src_off;
+    unsigned long long dst_off;
+    unsigned long long n;
+    unsigned long long nwv;         // widened: wide vectors wholly below the count
+    unsigned long long unit_begin;  // units owned by the entries before this one
+    unsigned int what;              // narrow kind * 8 + wide kind, or kUnpackWidenCopyUnit
+    unsigned int rem;               // widened: 4-byte words of the partial wide vector
+};
+static const unsigned int kUnpackWidenCopyUnit = 0xFFu;
+#define CSP_UNPACK_WIDEN_WHAT(N, W) (unsigned int)(CSP_KIND_##N * 8 + CSP_KIND_##W)
+static_assert(4 * kNarrowStepsPerWave * kNarrowStepVecs * 16 + 64 <= 160 * 1024 / 8,
+              "eight workgroups per CU");
+
+// One narrow tile of a WIDEN segment for one wave: the fragment above, with
+// the arena-global word index and the master as the second destination
+template <int NARROW, int WIDE, typename Strips>
+__device__ __forceinline__ void unpack_widen_tile(const CSP_GLOBAL u32x4* __restrict__ src,
+                                                  size_t nnv, CSP_GLOBAL u32x4* __restrict__ dst,
+                                                  CSP_GLOBAL u32x4* __restrict__ mst, size_t nwv,
+                                                  unsigned int rem, size_t tile,
+                                                  unsigned int word_base, Strips& strip,
+                                                  unsigned int lane, unsigned int wave,
+                                                  unsigned long long& s0, unsigned long long& t) {
+    typedef Widen<NARROW, WIDE> W;
+    constexpr int R = W::R, U = W::kUnroll;
+    typedef typename W::piece_t piece_t;
+    CSP_WIDEN_WAVE_STEPS(tile, word_base, if (mst != nullptr) mst[wv] = o;)
+}
+
+__global__ __launch_bounds__(256) void csp_unpack_widen_checksum_kernel(
+    const UnpackWidenEntry* __restrict__ segs, unsigned int nseg, unsigned long long total_units,
+    const unsigned char* __restrict__ arena, unsigned char* __restrict__ master,
+    unsigned long long* __restrict__ out) {
+    __shared__ u32x4 strip[4][kNarrowStepsPerWave][kNarrowStepVecs];  // the largest trip
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = threadIdx.x >> 6;
+    unsigned long long s0 = 0, t = 0;
+    for (unsigned long long unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
+        // last entry whose first unit is <= unit (unit_begin is strictly
+        // increasing: the host leaves empty segments out of the table)
+        unsigned int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) / 2;
+            if (segs[mid].unit_begin <= unit) lo = mid; else hi = mid;
+        }
+        const UnpackWidenEntry& e = segs[lo];
+        const unsigned long long u = unit - e.unit_begin;
+        const unsigned long long dst_off = e.dst_off;
+        // wide-arena index of the segment's first word
+        const unsigned int word_base = (unsigned int)(dst_off / 4);
+        const CSP_GLOBAL u32x4* src = reinterpret_cast<const CSP_GLOBAL u32x4*>(
+            (const CSP_GLOBAL unsigned char*)(arena + e.src_off));
+        // null without a master: uniform for the grid
+        CSP_GLOBAL u32x4* mst = master == nullptr ? nullptr
+            : reinterpret_cast<CSP_GLOBAL u32x4*>((CSP_GLOBAL unsigned char*)(master + dst_off));
+        const unsigned int what = e.what;
+        if (what == kUnpackWidenCopyUnit) {
+            const unpack_dst_t dst = (unpack_dst_t)e.dst;
+            const unsigned long long nbytes = e.n;
+            const size_t nfull = nbytes / 16;  // vectors wholly inside the segment
+            const unsigned int tail = (unsigned int)(nbytes % 16);
+            const size_t nvec = nfull + (tail ? 1 : 0);  // vectors the segment owns
+            const size_t v0 = u * kPackTileVecs + threadIdx.x;
+            if ((u + 1) * kPackTileVecs <= nfull) {
+                // interior tile: every lane has four whole vectors
+                u32x4 v[kPackUnroll];
+#pragma unroll
+                for (int k = 0; k < kPackUnroll; ++k) v[k] = src[v0 + k * 256];
+                if (mst != nullptr) {
+#pragma unroll
+                    for (int k = 0; k < kPackUnroll; ++k) mst[v0 + k * 256] = v[k];
+                }
+#pragma unroll
+                for (int k = 0; k < kPackUnroll; ++k) {
+                    const size_t vi = v0 + k * 256;
+                    __builtin_nontemporal_store(
+                        v[k], reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+                    checksum_add(s0, t, v[k], word_base + (unsigned int)(vi * 4));
+                }
+                continue;
+            }
+#pragma unroll
+            for (int k = 0; k < kPackUnroll; ++k) {
+                const size_t vi = v0 + k * 256;
+                if (vi >= nvec) continue;
+                const u32x4 v = src[vi];  // padding included: all 16 bytes are arena
+                if (mst != nullptr) mst[vi] = v;
+                checksum_add(s0, t, v, word_base + (unsigned int)(vi * 4));
+                if (vi < nfull)
+                    __builtin_nontemporal_store(
+                        v, reinterpret_cast<CSP_GLOBAL u32x4*>(dst + vi * 16));
+                else
+                    unpack_store_tail(dst + vi * 16, v, tail);
+            }
+            continue;
+        }
+        CSP_GLOBAL u32x4* dst = reinterpret_cast<CSP_GLOBAL u32x4*>((unpack_dst_t)e.dst);
+        const unsigned long long nnv = e.n, nwv = e.nwv;
+        const unsigned int rem = e.rem;
+#define CSP_UNPACK_WIDEN_CASE(N, W)                                                             \
+    case CSP_UNPACK_WIDEN_WHAT(N, W):                                                           \
+        unpack_widen_tile<CSP_KIND_##N, CSP_KIND_##W>(src, nnv, dst, mst, nwv, rem, u,          \
+                                                      word_base, strip, lane, wave, s0, t);     \
+        break;
+        switch (what) {  // the host admits kWidenPairs only
+            CSP_UNPACK_WIDEN_CASE(BF16, F32)
+            CSP_UNPACK_WIDEN_CASE(F32, F64)
+            CSP_UNPACK_WIDEN_CASE(I32, I64)
+            CSP_UNPACK_WIDEN_CASE(I16, I64)
+            CSP_UNPACK_WIDEN_CASE(U8, I64)
+            CSP_UNPACK_WIDEN_CASE(I16, I32)
+            CSP_UNPACK_WIDEN_CASE(U8, I32)
+        }
+#undef CSP_UNPACK_WIDEN_CASE
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+static const size_t kUnpackWidenGridCapDefault = 1024;
+static size_t g_unpack_widen_grid_cap = kUnpackWidenGridCapDefault;
+// the dispatcher's PACK_ARGS_MAX_BYTES: every wide word index stays below 2^30
+static const uint64_t kUnpackWidenMaxWideBytes = uint64_t(4) << 30;
+
+// Tools only: the grid cap of the next csp_unpack_widen_checksum_dev calls (0
+// restores the default).  Returns the cap in effect.  With a cap of 1, 2 or 3
+// every workgroup walks units of both kinds in turn.
+extern "C" size_t csp_unpack_widen_checksum_grid_cap(size_t cap) {
+    g_unpack_widen_grid_cap =
+        cap ? std::min(cap, size_t(65536)) : kUnpackWidenGridCapDefault;
+    return g_unpack_widen_grid_cap;
+}
+
+// Unpack the narrow arena's nseg segments into dst[k] at full width and, with
+// `master` set, into the master as well, and put csp_checksum_dev(wide arena,
+// wide_bytes) into out[2], from ONE launch.  Segment k is copied byte for
+// byte (narrow_kind CSP_UNPACK_WIDEN_COPY: count bytes) or widened from
+// narrow_kind to wide_kind (a pair of csp_widen_checksum_dev: count elements).
+// Both layouts follow csp_pack_dev's rule: src_off over the bytes the segments
+// have in the narrow arena, dst_off over their full-width bytes, each at the
+// next multiple of 16 after the one before; narrow_bytes and wide_bytes are
+// the totals.  Exactly the segment's full-width bytes are written at dst[k];
+// the master is written whole, the padding after a widened segment zero, after
+// a copy as the arena has it; the narrow arena is only read, and the pad bytes
+// after a widened segment may hold anything.  An empty segment owns no unit
+// and its dst may be null.  Returns 0, or -1 with a message that names the
+// segment and nothing launched for: a null out or segs; 2^31 segments or more;
+// a narrow arena or master that is not 16-byte aligned or overflows; a pair
+// that is not served; a count above what wide_bytes allows; a dst that is not
+// 16-byte aligned, is null for a non-empty segment or overflows; a src_off or
+// dst_off that is not where its layout rule puts it; a narrow_bytes or
+// wide_bytes that is not its layout's total; wide_bytes above 4 GiB; a null
+// narrow arena for a non-zero narrow_bytes; any overlap among the narrow arena,
+// the master and a destination; and for a HIP failure.  Overlap BETWEEN
+// destinations is the caller's responsibility, as in csp_unpack_checksum_dev.
+// wide_bytes == 0 gives out = (0, 0).  Runs on copy_stream(), so it is ordered
+// after the copies csp_h2d_stream_fd issued, and synchronises that stream
+// before returning; buffers in use on another stream must be complete first.
+// kernel_ms (optional): the kernel alone, from events around the launch.
+extern "C" int csp_unpack_widen_checksum_dev(const CspUnpackWidenSeg* segs, size_t nseg,
+                                             const void* narrow_arena, size_t narrow_bytes,
+                                             void* master, size_t wide_bytes, uint64_t out[2],
+                                             double* kernel_ms) {
+    const char* fn = "csp_unpack_widen_checksum_dev";
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (out == nullptr) {
+        snprintf(g_err, sizeof(g_err), "%s: null output pointer", fn);
+        return -1;
+    }
+    out[0] = out[1] = 0;
+    if (nseg >= (size_t(1) << 31)) {  // before anything walks the segments
+        snprintf(g_err, sizeof(g_err), "%s: %zu segments are too many", fn, nseg);
+        return -1;
+    }
+    if (nseg != 0 && segs == nullptr) {
+        snprintf(g_err, sizeof(g_err), "%s: null segs pointer", fn);
+        return -1;
+    }
+    if ((uint64_t)wide_bytes > kUnpackWidenMaxWideBytes) {
+        snprintf(g_err, sizeof(g_err), "%s: wide_bytes %zu is above 4 GiB", fn, wide_bytes);
+        return -1;
+    }
+    const uintptr_t a = reinterpret_cast<uintptr_t>(narrow_arena);
+    const uintptr_t m = reinterpret_cast<uintptr_t>(master);
+    if (a % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: narrow arena pointer %p is not 16-byte aligned", fn,
+                 narrow_arena);
+        return -1;
+    }
+    if (m % 16 != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: master pointer %p is not 16-byte aligned", fn, master);
+        return -1;
+    }
+    if (a + narrow_bytes < a || m + wide_bytes < m) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes at narrow arena %p or %zu at master %p "
+                 "overflow", fn, narrow_bytes, narrow_arena, wide_bytes, master);
+        return -1;
+    }
+    auto overlap = [](uintptr_t p, uint64_t np, uintptr_t q, uint64_t nq) {
+        return np != 0 && nq != 0 && p < q + nq && q < p + np;
+    };
+    std::vector<UnpackWidenEntry> table;
+    table.reserve(nseg);
+    uint64_t narrow_at = 0, wide_at = 0, units = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        const CspUnpackWidenSeg& g = segs[k];
+        const bool copy = g.narrow_kind == CSP_UNPACK_WIDEN_COPY;
+        const WidenPairInfo* pair = nullptr;
+        for (const WidenPairInfo& p : kWidenPairs)
+            if (!copy && p.narrow_kind == g.narrow_kind && p.wide_kind == g.wide_kind) pair = &p;
+        if (!copy && pair == nullptr) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu: no widening from kind %d to kind %d",
+                     fn, k, g.narrow_kind, g.wide_kind);
+            return -1;
+        }
+        const uint64_t wes = copy ? 1 : pair->wide_es, nes = copy ? 1 : pair->narrow_es;
+        if (g.count > ((uint64_t)wide_bytes - std::min<uint64_t>(wide_at, wide_bytes)) / wes) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: segment %zu: %llu elements of %llu bytes at %llu end past wide_bytes "
+                     "%zu", fn, k, (unsigned long long)g.count, (unsigned long long)wes,
+                     (unsigned long long)wide_at, wide_bytes);
+            return -1;
+        }
+        const uint64_t wide_n = g.count * wes, narrow_n = g.count * nes;
+        if (g.src_off != narrow_at) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: segment %zu: src_off is %llu, the narrow layout gives %llu", fn, k,
+                     (unsigned long long)g.src_off, (unsigned long long)narrow_at);
+            return -1;
+        }
+        if (g.dst_off != wide_at) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: segment %zu: dst_off is %llu, the wide layout gives %llu", fn, k,
+                     (unsigned long long)g.dst_off, (unsigned long long)wide_at);
+            return -1;
+        }
+        const uint64_t narrow_rounded = (narrow_n + 15) & ~uint64_t(15);
+        narrow_at += narrow_rounded;
+        wide_at += (wide_n + 15) & ~uint64_t(15);
+        const uintptr_t d = reinterpret_cast<uintptr_t>(g.dst);
+        if (d % 16 != 0) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu: dst %p is not 16-byte aligned", fn, k,
+                     g.dst);
+            return -1;
+        }
+        if (g.count == 0) continue;  // owns no unit
+        if (d == 0) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu has %llu bytes and a null dst", fn, k,
+                     (unsigned long long)wide_n);
+            return -1;
+        }
+        if (d + wide_n < d) {
+            snprintf(g_err, sizeof(g_err), "%s: segment %zu: dst %p with %llu bytes overflows", fn,
+                     k, g.dst, (unsigned long long)wide_n);
+            return -1;
+        }
+        if (overlap(d, wide_n, a, narrow_bytes) ||
+            (m != 0 && overlap(d, wide_n, m, wide_bytes))) {
+            snprintf(g_err, sizeof(g_err),
+                     "%s: segment %zu: %llu bytes at dst %p overlap the narrow arena at %p or the "
+                     "master at %p", fn, k, (unsigned long long)wide_n, g.dst, narrow_arena,
+                     master);
+            return -1;
+        }
+        UnpackWidenEntry e = {};
+        e.dst = static_cast<unsigned char*>(g.dst);
+        e.src_off = g.src_off;
+        e.dst_off = g.dst_off;
+        e.unit_begin = units;
+        if (copy) {
+            e.what = kUnpackWidenCopyUnit;
+            e.n = narrow_n;
+        } else {
+            e.what = (unsigned int)(g.narrow_kind * 8 + g.wide_kind);
+            e.n = narrow_rounded / 16;
+            e.nwv = wide_n / 16;
+            e.rem = (unsigned int)(wide_n % 16 / 4);
+        }
+        units += (narrow_rounded + kPackTileBytes - 1) / kPackTileBytes;
+        table.push_back(e);
+    }
+    if (narrow_at != (uint64_t)narrow_bytes || wide_at != (uint64_t)wide_bytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: narrow_bytes is %zu and wide_bytes %zu, the segments need %llu and %llu", fn,
+                 narrow_bytes, wide_bytes, (unsigned long long)narrow_at,
+                 (unsigned long long)wide_at);
+        return -1;
+    }
+    if (table.empty()) return 0;
+    if (narrow_arena == nullptr) {
+        snprintf(g_err, sizeof(g_err), "%s: null narrow arena for %zu bytes", fn, narrow_bytes);
+        return -1;
+    }
+    if (m != 0 && overlap(a, narrow_bytes, m, wide_bytes)) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s: %zu bytes at narrow arena %p overlap %zu at master %p", fn, narrow_bytes,
+                 narrow_arena, wide_bytes, master);
+        return -1;
+    }
+
+    // one accumulator pair and one grow-only table per process, one call at
+    // a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static UnpackWidenEntry* dev_table = nullptr;
+    static size_t dev_cap = 0;  // entries
+    static int dev_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (dev_device != device) {
+        if (acc) (void)hipFree(acc);
+        if (dev_table) (void)hipFree(dev_table);
+        acc = nullptr;
+        dev_table = nullptr;
+        dev_cap = 0;
+        dev_device = device;
+    }
+    if (acc == nullptr) HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+    if (dev_table == nullptr || dev_cap < table.size()) {
+        if (dev_table) (void)hipFree(dev_table);
+        dev_table = nullptr;
+        dev_cap = 0;
+        size_t cap = 1024;
+        while (cap < table.size()) cap *= 2;
+        HIP_TRY(hipMalloc(&dev_table, cap * sizeof(UnpackWidenEntry)));
+        dev_cap = cap;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define UNPACKWIDEN_TRY(expr)                                      \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    // `table` outlives the copy: the stream is synchronised below
+    UNPACKWIDEN_TRY(hipMemcpyAsync(dev_table, table.data(),
+                                   table.size() * sizeof(UnpackWidenEntry),
+                                   hipMemcpyHostToDevice, s));
+    UNPACKWIDEN_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t blocks = (size_t)std::min<uint64_t>(units, g_unpack_widen_grid_cap);
+    if (t0) UNPACKWIDEN_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_unpack_widen_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0,
+                       s, dev_table, (unsigned int)table.size(), (unsigned long long)units,
+                       static_cast<const unsigned char*>(narrow_arena),
+                       static_cast<unsigned char*>(master), acc);
+    UNPACKWIDEN_TRY(hipGetLastError());
+    if (t1) UNPACKWIDEN_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    UNPACKWIDEN_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    UNPACKWIDEN_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) {
+        float ms = 0.f;
+        UNPACKWIDEN_TRY(hipEventElapsedTime(&ms, t0, t1));
+        *kernel_ms = ms;
+    }
+#undef UNPACKWIDEN_TRY
+    out[0] = host[0];
+    out[1] = host[1];
     return done(0);
 }
 

@@ -55,6 +55,17 @@ Protocol (all frames: 8-byte big-endian length + payload):
              scatters it into a private tensor per segment and yields the
              arena's checksum in the same pass.  Such an entry may carry
              "cache" like any other: the arena is then the master.  With
+             narrow_tensor_args as well, an entry whose bytes travel whole
+             may carry "wire_nbytes" and, on each narrowed element of
+             "packed", "wire": the ONE frame is then a narrow arena of
+             wire_nbytes bytes, the segments in order at the pack layout of
+             their bytes on the wire, and ONE
+             csp_unpack_widen_checksum_dev call writes every segment at
+             full width into its private tensor (with "store": into the
+             master too, which has the wide layout of "offset" and
+             "nbytes") and yields the checksum of the wide arena, which is
+             what "sum" announces; meta["arg_staging"] counts "widened"
+             (segments), "wire_bytes" and "widen_ms".  With
              the executor option patch_tensor_args it may instead carry
              "cache": {"key": NEW, "patch": {"base": BASE, "segments":
              [j, ...]}} and "patch_nbytes": its ONE frame is then a delta
@@ -453,6 +464,18 @@ def _load_gpu_lib():
             ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_uint64),
             ctypes.POINTER(ctypes.c_float),
+        ]
+    if hasattr(lib, "csp_unpack_widen_checksum_dev"):
+        lib.csp_unpack_widen_checksum_dev.restype = ctypes.c_int
+        lib.csp_unpack_widen_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_double),
         ]
     if GATHER_RESULTS and hasattr(lib, "csp_pack_gather_checksum_dev"):
         lib.csp_pack_gather_checksum_dev.restype = ctypes.c_int
@@ -1828,6 +1851,73 @@ def _unpack_arena(lib, index, arena, total, info, tensors, stage):
     return [int(out[0]), int(out[1])]
 
 
+def _packed_widen_pairs(lib, index, info):
+    """The WIDEN_PAIRS entry (None: a copy) of every segment of a packed entry
+    that carries ``"wire_nbytes"``; RuntimeError for a pair or a library that
+    cannot widen it, as in _widen_pair."""
+    pairs = []
+    for j, seg in enumerate(info["packed"]):
+        pair = None
+        if seg.get("wire") is not None:
+            pair = WIDEN_PAIRS.get((seg["wire"], seg["dtype"]))
+            if pair is None or int(seg["nbytes"]) % pair[3]:
+                raise RuntimeError(
+                    "argument buffer %d: no widening of segment %d from wire type %r to "
+                    "%d bytes of %s" % (index, j, seg["wire"], int(seg["nbytes"]), seg["dtype"])
+                )
+        pairs.append(pair)
+    if not hasattr(lib, "csp_unpack_widen_checksum_dev"):
+        raise RuntimeError(
+            "argument buffer %d arrived with narrowed segments and the GPU library has no "
+            "csp_unpack_widen_checksum_dev" % index
+        )
+    return pairs
+
+
+def _unpack_widen_arena(lib, index, narrow, wire_total, master, total, info, tensors, stage):
+    """ONE csp_unpack_widen_checksum_dev call: the segments of the narrow
+    arena ``narrow`` (``wire_total`` bytes, as they crossed the pipe) at full
+    width into ``tensors`` and, when given, into ``master`` (``total`` bytes,
+    the wide layout); returns [s0, s1] of the wide arena."""
+    import ctypes
+
+    class Seg(ctypes.Structure):  # CspUnpackWidenSeg
+        _fields_ = [("dst", ctypes.c_void_p), ("src_off", ctypes.c_uint64),
+                    ("dst_off", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                    ("narrow_kind", ctypes.c_int32), ("wide_kind", ctypes.c_int32)]
+
+    segs = info["packed"]
+    pairs = _packed_widen_pairs(lib, index, info)
+    table = (Seg * len(segs))()
+    src_off = 0
+    for row, seg, pair, t in zip(table, segs, pairs, tensors):
+        nbytes = int(seg["nbytes"])
+        row.dst = (t.data_ptr() or None) if nbytes else None
+        row.src_off = src_off
+        row.dst_off = int(seg["offset"])
+        row.count = nbytes if pair is None else nbytes // pair[3]
+        row.narrow_kind, row.wide_kind = (-1, 0) if pair is None else pair[:2]
+        src_off += (row.count * (1 if pair is None else pair[2]) + 15) // 16 * 16
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_double()
+    rc = lib.csp_unpack_widen_checksum_dev(
+        table, len(segs), ctypes.c_void_p(narrow.data_ptr()), wire_total,
+        ctypes.c_void_p(master.data_ptr() if master is not None else None), total,
+        out, ctypes.byref(kernel_ms),
+    )
+    if rc != 0:
+        raise RuntimeError(
+            "argument buffer %d: csp_unpack_widen_checksum_dev failed: %s"
+            % (index, lib.csp_last_error().decode(errors="replace"))
+        )
+    stage["packed_tensors"] = stage.get("packed_tensors", 0) + len(segs)
+    stage["packed_bytes"] = stage.get("packed_bytes", 0) + sum(int(seg["nbytes"]) for seg in segs)
+    stage["widened"] = stage.get("widened", 0) + sum(pair is not None for pair in pairs)
+    stage["wire_bytes"] = stage.get("wire_bytes", 0) + wire_total
+    stage["widen_ms"] = stage.get("widen_ms", 0.0) + kernel_ms.value
+    return [int(out[0]), int(out[1])]
+
+
 def _packed_args_from_cache(lib, index, info, total, key, stage, report):
     """A ``ref`` packed entry: no frame, the tensors are unpacked from the
     cached arena and the arena verified in the same pass.  A miss is what it
@@ -2222,6 +2312,16 @@ def _receive_packed_device_args(index, info, stage, report):
         return _patch_packed_args(lib, index, info, total, cache, stage, report)
     if cache.get("rebase"):
         return _rebase_packed_args(lib, index, info, total, cache, stage, report)
+    wire_total = None
+    if info.get("wire_nbytes") is not None and total:
+        # narrow_tensor_args: the frame is the narrow arena
+        try:
+            _packed_widen_pairs(lib, index, info)
+        except RuntimeError:
+            if _read_frame(0) is None:  # drain with the Python reader
+                os._exit(4)
+            raise
+        wire_total = int(info["wire_nbytes"])
     key = None
     master = None
     if cache.get("store") and "sum" in info and total:
@@ -2239,7 +2339,10 @@ def _receive_packed_device_args(index, info, stage, report):
     arena = master
     tensors = None
     try:
-        if arena is None:
+        if wire_total is not None:
+            # transient: the one call below widens it into the tensors and the master
+            arena = _alloc_device_arg({"shape": [wire_total]}, torch.uint8, report)
+        elif arena is None:
             arena = _alloc_device_arg({"shape": [total]}, torch.uint8, report)
         tensors = _alloc_packed_tensors(info, report)
     except Exception as e:  # noqa: BLE001 - e.g. out of HBM
@@ -2247,12 +2350,12 @@ def _receive_packed_device_args(index, info, stage, report):
         if master is not None:
             report["not_stored"].append(key)
         arena = master = None
+    frame_bytes = total if wire_total is None else wire_total
     read_ms = ctypes.c_double()
     h2d_ms = ctypes.c_double()
     rc = lib.csp_h2d_stream_fd(
-        0, ctypes.c_void_p(arena.data_ptr() if (arena is not None and total) else 0),
-        total, min(STREAM_CHUNK, PACKED_ARG_CHUNK) if STREAM_CHUNK > 0 else PACKED_ARG_CHUNK, -1,
-        ctypes.byref(read_ms), ctypes.byref(h2d_ms),
+        0, ctypes.c_void_p(arena.data_ptr() if (arena is not None and frame_bytes) else 0),
+        frame_bytes, _packed_chunk(), -1, ctypes.byref(read_ms), ctypes.byref(h2d_ms),
     )
     stage["read_ms"] += read_ms.value
     stage["h2d_ms"] += h2d_ms.value
@@ -2271,7 +2374,13 @@ def _receive_packed_device_args(index, info, stage, report):
             "argument buffer %d: H2D copy failed (rc=%d): %s"
             % (index, rc, lib.csp_last_error().decode(errors="replace"))
         )
-    got = _unpack_arena(lib, index, arena, total, info, tensors, stage)
+    if wire_total is None:
+        got = _unpack_arena(lib, index, arena, total, info, tensors, stage)
+    else:
+        got = _unpack_widen_arena(
+            lib, index, arena, wire_total, master, total, info, tensors, stage
+        )
+    del arena
     stage["mode"] = "pinned-h2d"
     stage["tensors"] += 1
     stage["bytes"] += total
@@ -2349,18 +2458,27 @@ def _device_args_in_child(frames, meta_list, stage):
         if "packed" in info:
             # one .cuda() for the arena, then the same single unpack call
             total = int(info["nbytes"])
+            # narrow_tensor_args: the frame is the narrow arena, widened by the
+            # same single call as in persistent mode, with no master
+            wire_total = info.get("wire_nbytes") if total else None
+            frame_bytes = total if wire_total is None else int(wire_total)
             t0 = time.monotonic()
-            if len(frames[i]) != total:
+            if len(frames[i]) != frame_bytes:
                 raise RuntimeError(
                     "argument buffer %d: the packed frame has %d bytes, its "
-                    "entry announces %d" % (i, len(frames[i]), total)
+                    "entry announces %d" % (i, len(frames[i]), frame_bytes)
                 )
             arena = torch.frombuffer(frames[i], dtype=torch.uint8).cuda()
             tensors = _alloc_packed_tensors(info, _new_arg_cache_report())
             # the library's copy stream does not wait on the null stream
             torch.cuda.synchronize()
             stage["h2d_ms"] += (time.monotonic() - t0) * 1000
-            got = _unpack_arena(lib, i, arena, total, info, tensors, stage)
+            if wire_total is None:
+                got = _unpack_arena(lib, i, arena, total, info, tensors, stage)
+            else:
+                got = _unpack_widen_arena(
+                    lib, i, arena, frame_bytes, None, total, info, tensors, stage
+                )
             stage["mode"] = "isolated-copy"
             stage["tensors"] += 1
             stage["bytes"] += total

@@ -344,9 +344,80 @@ def packed_content_key(segment_keys) -> str:
     return outer.hexdigest()
 
 
+def narrow_packed_args(packed, views, stats: Optional[dict] = None):
+    """``pack_tensor_args`` with ``narrow_tensor_args``: the frame of a packed
+    arena whose bytes travel whole, every qualifying segment narrowed.
+    ``packed`` is the entry's segment list, ``views`` the segments' contiguous
+    bytes.  A segment qualifies when its dtype is in
+    ``native_io.NARROW_TARGETS``, :func:`narrow_arg` finds a lossless target
+    and its narrow size rounded to 16 is smaller than its wide size rounded to
+    16 (a segment that cannot meet that even at its narrowest target is not
+    read at all).  The segments are narrowed on the thread pool, one
+    ``native_io.narrow`` pass sequence each.  Returns ``(wire, frame,
+    wire_nbytes)``: per segment the wire dtype name or ``None``, a
+    :class:`FrameParts` with the segments in order at the pack layout of the
+    bytes they occupy on the wire (narrow buffers and untouched views, zero
+    padded), and its total; ``None`` when no segment is narrowed.  ``stats``
+    gets ``arg_narrowed`` (segments), ``arg_narrow_saved_bytes`` (frame bytes
+    left out) and ``arg_narrow_ms`` (the whole pass)."""
+    sizes = native_io.NARROW_ELEM_SIZE
+
+    def rounded(n):
+        return -(-n // PACK_ALIGN) * PACK_ALIGN
+
+    def candidate(seg):
+        targets = native_io.NARROW_TARGETS.get(seg["dtype"])
+        n = seg["nbytes"]
+        return bool(targets) and rounded(n // sizes[seg["dtype"]] * sizes[targets[0]]) < rounded(n)
+
+    def one(j):
+        if not candidate(packed[j]):
+            return None
+        # threads=1: already on the pool, whose workers must not wait for it
+        got = narrow_arg(views[j], packed[j]["dtype"], threads=1)
+        if got is None or rounded(len(got[1])) >= rounded(packed[j]["nbytes"]):
+            return None
+        return got
+
+    if not any(candidate(seg) for seg in packed):
+        return None
+    started = time.perf_counter()
+    narrowed = _map(one, list(range(len(packed))), None)
+    parts = []
+    total = saved = 0
+    for seg, view, got in zip(packed, views, narrowed):
+        part = view if got is None else got[1]
+        n = memoryview(part).nbytes
+        parts.append(part)
+        if n % PACK_ALIGN:
+            parts.append(bytes(PACK_ALIGN - n % PACK_ALIGN))
+        total += rounded(n)
+        saved += rounded(seg["nbytes"]) - rounded(n)
+    count = sum(got is not None for got in narrowed)
+    if stats is not None:
+        stats["arg_narrow_ms"] = (
+            stats.get("arg_narrow_ms", 0.0) + (time.perf_counter() - started) * 1e3
+        )
+        stats["arg_narrowed"] = stats.get("arg_narrowed", 0) + count
+        stats["arg_narrow_saved_bytes"] = stats.get("arg_narrow_saved_bytes", 0) + saved
+    if not count:
+        return None
+    return [got and got[0] for got in narrowed], FrameParts(parts), total
+
+
+def _narrowed_packed_entry(info, wire, wire_nbytes):
+    """``info`` with ``"wire"`` on each narrowed ``packed`` element and
+    ``"wire_nbytes"``, the frame's bytes; everything else stays the wide
+    arena's."""
+    return dict(
+        info, wire_nbytes=wire_nbytes,
+        packed=[dict(seg, wire=w) if w else seg for seg, w in zip(info["packed"], wire)],
+    )
+
+
 def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
                      buffers, buffer_meta, patch_max_fraction=None, rebase=False,
-                     retain=False):
+                     retain=False, narrow=False, narrow_stats=None):
     """The ``pack_tensor_args`` half of :func:`extract_arg_buffers`: emit the
     packed entry when the rule in its docstring holds.  Returns
     ``{id(tensor): marker}``, empty when nothing is packed.  Only called with
@@ -359,7 +430,12 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
     frame (the tensor's own memory and its zero padding), and the
     fraction; with ``rebase`` (``rebase_tensor_args``) also ``"rebase":
     True``, and with ``retain`` (``retain_tensor_results``) ``"retain":
-    True``."""
+    True``.
+
+    With ``narrow`` (``narrow_tensor_args``) an uncached arena is narrowed
+    here (:func:`narrow_packed_args`); a cacheable one is only marked
+    ``cache["narrow"]`` and keeps ``cache["seg_views"]``, and
+    :meth:`_ArgCacheSend.frames` narrows it when its bytes travel whole."""
     import ctypes
 
     import torch
@@ -440,8 +516,17 @@ def _pack_small_args(args, kwargs, threshold, cache_min_bytes, pack_min_bytes,
                     info["cache"]["rebase"] = True
                 if retain:
                     info["cache"]["retain"] = True
+    frame = FrameParts(parts)
+    if narrow and "sum" in info:
+        if "cache" in info:  # decided when the bytes travel, not for a ref or a delta
+            info["cache"].update(narrow=True, seg_views=views)
+        else:
+            got = narrow_packed_args(info["packed"], views, narrow_stats)
+            if got is not None:
+                info = _narrowed_packed_entry(info, got[0], got[2])
+                frame = got[1]
     # the source tensors stay alive until the frame is drained
-    buffers.append((FrameParts(parts), srcs))
+    buffers.append((frame, srcs))
     buffer_meta.append(info)
     index = len(buffers) - 1
     for j, t in enumerate(tensors):
@@ -523,7 +608,15 @@ def extract_arg_buffers(
     GPU.  A cacheable entry is only marked here and narrowed by
     :meth:`_ArgCacheSend.frames` when its bytes actually travel; its buffer
     stays the wide view.  ``narrow_stats``: see :func:`narrow_arg`.  Without
-    ``libcsp_io.so`` nothing is narrowed."""
+    ``libcsp_io.so`` nothing is narrowed.  With ``pack_min_bytes`` as well, the
+    segments of a packed arena that :func:`narrow_packed_args` admits travel
+    narrow inside the one frame: each gains ``"wire"``, the entry gains
+    ``"wire_nbytes"`` (the frame's bytes), and ``offset``, ``nbytes``, ``sum``
+    and ``cache.key`` stay those of the wide arena, which is what the worker's
+    ``csp_unpack_widen_checksum_dev`` rebuilds, caches and sums.  Only an arena
+    whose bytes travel whole is narrowed: a transient one here, a cached one
+    when it is stored; a reference, a patch and a rebase are as without the
+    option."""
     import sys
 
     if "torch" not in sys.modules:
@@ -539,6 +632,7 @@ def extract_arg_buffers(
         packed_markers = _pack_small_args(
             args, kwargs, threshold, cache_min_bytes, pack_min_bytes, buffers, buffer_meta,
             patch_max_fraction=patch_max_fraction, rebase=rebase, retain=retain,
+            narrow=narrow, narrow_stats=narrow_stats,
         )
 
     def extract(t):
@@ -1117,7 +1211,15 @@ class _ArgCacheSend:
                         {"key": self._wire(key), "ref": True} if ref
                         else {"key": key, "store": True}
                     )
-                    if not ref and cache.get("narrow"):
+                    if not ref and cache.get("narrow") and "packed" in info:
+                        # a whole arena travels: its segments are narrowed now
+                        got = narrow_packed_args(
+                            info["packed"], cache["seg_views"], self.cache_stats
+                        )
+                        if got is not None:
+                            info = _narrowed_packed_entry(info, got[0], got[2])
+                            self.narrowed[index] = (None, got[1])
+                    elif not ref and cache.get("narrow"):
                         # narrow_tensor_args: these bytes travel, so narrow now
                         self.narrowed[index] = narrow_arg(
                             self.views[index], info["dtype"], stats=self.cache_stats
