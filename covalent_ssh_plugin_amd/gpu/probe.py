@@ -42,6 +42,9 @@ gfx950 only) provides:
 * ``csp_widen_checksum_dev`` — the inverse for arguments: narrow bytes in HBM
   widened into one or two destinations and checksummed by one launch
   (``narrow_tensor_args``),
+* ``csp_bool_pack_checksum_dev`` / ``csp_bool_unpack_checksum_dev`` — a bool
+  tensor packed to one bit per element, tested and checksummed by one launch,
+  and the inverse into one or two destinations (both options),
 * ``csp_hbm_sweep_dev`` — one launch of the probe's HBM sweep kernel on the
   caller's buffers, and ``csp_checksum_grid_cap`` /
   ``csp_copy_checksum_grid_cap`` / ``csp_unpack_checksum_grid_cap`` (tools
@@ -335,6 +338,28 @@ def load(path: str = "") -> ctypes.CDLL:
     ]
     lib.csp_widen_checksum_grid_cap.restype = ctypes.c_size_t
     lib.csp_widen_checksum_grid_cap.argtypes = [ctypes.c_size_t]
+    lib.csp_bool_pack_checksum_dev.restype = ctypes.c_int
+    lib.csp_bool_pack_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_float),
+    ]
+    lib.csp_bool_unpack_checksum_dev.restype = ctypes.c_int
+    lib.csp_bool_unpack_checksum_dev.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_size_t,
+        ctypes.c_void_p,
+        ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_float),
+    ]
+    for name in ("csp_bool_pack_checksum_grid_cap", "csp_bool_unpack_checksum_grid_cap"):
+        getattr(lib, name).restype = ctypes.c_size_t
+        getattr(lib, name).argtypes = [ctypes.c_size_t]
     lib.csp_unpack_widen_checksum_dev.restype = ctypes.c_int
     lib.csp_unpack_widen_checksum_dev.argtypes = [
         ctypes.POINTER(UnpackWidenSeg),
@@ -1093,6 +1118,69 @@ def unpack_widen_checksum_grid_cap(cap: int = 0) -> int:
     """Tools only: set the grid cap of :func:`unpack_widen_checksum_device` (0
     restores the shipped default).  Returns the cap in effect."""
     return int(load().csp_unpack_widen_checksum_grid_cap(int(cap)))
+
+
+def bool_bits_bytes(numel: int) -> int:
+    """Bytes of ``numel`` bool elements as ``"bits"`` in a device buffer: one
+    bit each, zero padded to 16 bytes."""
+    return ((numel + 7) // 8 + 15) // 16 * 16
+
+
+def bool_pack_checksum_device(src_ptr: int, numel: int, dst_ptr: int = 0, dst_bytes: int = 0) -> dict:
+    """Test the ``numel`` bool bytes at device pointer ``src_ptr`` for the
+    ``"bits"`` form (``narrow_tensor_results``).  Returns ``{"rc", "bad", "sum",
+    "kernel_ms"}``; ``bad`` is the OR of ``byte & 0xFE`` over all bytes, 0 iff
+    every byte is 0 or 1.  With ``dst_ptr`` 0 the call is a probe and stores
+    nothing.  With ``dst_ptr`` set, element ``i`` is written as bit ``i % 8`` of
+    byte ``i // 8`` (``numpy.packbits(bitorder="little")``) in the same kernel
+    launch, zero padded to ``dst_bytes == bool_bits_bytes(numel)``, and ``sum``
+    equals ``checksum_device(dst_ptr, dst_bytes)`` when ``bad`` is 0.  A null or
+    misaligned pointer, a wrong ``dst_bytes``, more than 16 GiB or overlapping
+    buffers raise ``GpuLibError`` and launch nothing.  Runs on the library's
+    copy stream; a source written on another stream must be complete first."""
+    lib = load()
+    out = (ctypes.c_uint64 * 2)()
+    bad = ctypes.c_uint32()
+    kernel_ms = ctypes.c_float()
+    rc = lib.csp_bool_pack_checksum_dev(
+        ctypes.c_void_p(src_ptr or None), numel, ctypes.c_void_p(dst_ptr or None), dst_bytes,
+        out, ctypes.byref(bad), ctypes.byref(kernel_ms),
+    )
+    _check(lib, rc, "csp_bool_pack_checksum_dev")
+    return {"rc": rc, "bad": bad.value, "sum": (int(out[0]), int(out[1])),
+            "kernel_ms": kernel_ms.value}
+
+
+def bool_unpack_checksum_device(src_ptr: int, numel: int, dst_ptr: int, dst2_ptr: int = 0) -> dict:
+    """Unpack the ``numel`` elements held as ``"bits"`` at device pointer
+    ``src_ptr`` into bool bytes at ``dst_ptr`` and, when set, ``dst2_ptr`` as
+    well, in one kernel launch (``narrow_tensor_args``).  Returns ``{"rc",
+    "sum", "kernel_ms"}``; ``sum`` equals ``checksum_device(dst_ptr, numel)``.
+    The source must be readable up to ``bool_bits_bytes(numel)``, its pad bits
+    and pad bytes may hold anything; the destinations are exactly ``numel``
+    bytes.  A null or misaligned pointer, more than 16 GiB or overlapping
+    buffers raise ``GpuLibError`` and launch nothing."""
+    lib = load()
+    out = (ctypes.c_uint64 * 2)()
+    kernel_ms = ctypes.c_float()
+    rc = lib.csp_bool_unpack_checksum_dev(
+        ctypes.c_void_p(src_ptr or None), numel, ctypes.c_void_p(dst_ptr or None),
+        ctypes.c_void_p(dst2_ptr or None), out, ctypes.byref(kernel_ms),
+    )
+    _check(lib, rc, "csp_bool_unpack_checksum_dev")
+    return {"rc": rc, "sum": (int(out[0]), int(out[1])), "kernel_ms": kernel_ms.value}
+
+
+def bool_pack_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`bool_pack_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_bool_pack_checksum_grid_cap(int(cap)))
+
+
+def bool_unpack_checksum_grid_cap(cap: int = 0) -> int:
+    """Tools only: set the grid cap of :func:`bool_unpack_checksum_device` (0
+    restores the shipped default).  Returns the cap in effect."""
+    return int(load().csp_bool_unpack_checksum_grid_cap(int(cap)))
 
 
 GATHER_PATHS = {0: "none", 1: "direct", 2: "direct16", 3: "transpose", 5: "slab"}

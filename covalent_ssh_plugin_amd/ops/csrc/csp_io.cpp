@@ -14,6 +14,8 @@
 //   csp_io_narrow      one pass over a chunk of a tensor argument: tests it
 //                      for lossless narrowing and writes the narrow elements
 //                      (narrow_tensor_args; the worker widens on the GPU)
+//   csp_io_bool_pack   the same for a chunk of a bool tensor: every byte
+//                      tested for 0 or 1 and eight of them packed into one
 //
 // Return codes: see csp_io.h.
 
@@ -61,6 +63,11 @@ void csp_io_checksum(const void* src, size_t n, uint64_t out[2]) {
 int csp_io_narrow(const void* src, size_t numel, int src_kind, int dst_kind, void* dst,
                   uint64_t* bad) {
     return csp_io_detail::narrow(src, numel, src_kind, dst_kind, dst, bad);
+}
+
+// One chunk of a bool argument packed to bits (definition in csp_io.h).
+int csp_io_bool_pack(const void* src, size_t numel, void* dst, uint64_t* bad) {
+    return csp_io_detail::bool_pack(src, numel, dst, bad);
 }
 
 }  // extern "C"

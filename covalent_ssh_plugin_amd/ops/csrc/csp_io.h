@@ -252,4 +252,42 @@ static inline int narrow(const void* src, size_t numel, int src_kind, int dst_ki
     return -1;
 }
 
+// The host half of the "bits" wire format (bool tensors under
+// narrow_tensor_args), what csp_bool_pack_checksum_kernel in csp_gpu.hip does
+// to a result: element i is bit i % 8 of byte i / 8, as numpy.packbits with
+// bitorder="little".  A bool tensor is exact iff every storage byte is 0 or 1;
+// `bad` gets the OR of byte & 0xFE.  A caller that cuts a tensor into pieces
+// starts every piece on a multiple of 8 elements, so that no two pieces share
+// an output byte.  With dst set, (numel + 7) / 8 bytes are written, the pad
+// bits of the last one zero, whatever the verdict.  Returns 0, or -1 for a
+// null bad.
+static inline int bool_pack(const void* src, size_t numel, void* dst, uint64_t* bad) {
+    if (bad == nullptr) return -1;
+    const unsigned char* p = static_cast<const unsigned char*>(src);
+    unsigned char* q = static_cast<unsigned char*>(dst);
+    uint64_t b = 0;
+    size_t i = 0;
+    for (; i + 8 <= numel; i += 8) {
+        uint64_t w;
+        memcpy(&w, p + i, 8);  // little-endian hosts only
+        b |= w & 0xFEFEFEFEFEFEFEFEull;
+        // bit 8 * j of w to bit 56 + j: the products' bits do not collide
+        const uint64_t bits = (w & 0x0101010101010101ull) * 0x0102040810204080ull;
+        if (q) q[i / 8] = (unsigned char)(bits >> 56);
+    }
+    if (i < numel) {
+        unsigned char o = 0;
+        for (size_t j = i; j < numel; ++j) {
+            b |= p[j] & 0xFEu;
+            o |= (unsigned char)((p[j] & 1u) << (j - i));
+        }
+        if (q) q[i / 8] = o;
+    }
+    b |= b >> 32;  // the eight byte lanes of the word loop folded into one
+    b |= b >> 16;
+    b |= b >> 8;
+    *bad |= b & 0xFEu;
+    return 0;
+}
+
 }  // namespace csp_io_detail

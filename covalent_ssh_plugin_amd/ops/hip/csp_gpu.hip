@@ -6179,6 +6179,500 @@ extern "C" int csp_unpack_widen_checksum_dev(const CspUnpackWidenSeg* segs, size
     return done(0);
 }
 
+// ---------------------------------------------------------------------------
+// bool tensors as bits: pack with checksum (results), unpack with checksum
+// (arguments)
+// ---------------------------------------------------------------------------
+//
+// A torch.bool tensor (an attention or padding mask, the output of x > 0)
+// costs one byte per element in HBM and carries one bit.  On the wire it
+// travels as "bits": element i of the contiguous tensor is bit i % 8 of byte
+// i / 8 (numpy.packbits with bitorder="little"), ceil(numel / 8) bytes, zero
+// padded to a multiple of 16.  The form is exact iff every storage byte is 0
+// or 1; a uint8 tensor viewed as bool can hold other values, and the OR of
+// byte & 0xFE over all bytes, `bad`, tells.
+//
+// The element is smaller than a byte, so these are not further Narrow<> /
+// Widen<> pairs: sizes are not numel * element size, both buffers end on any
+// byte (the bits on any bit), and the work is cut on the WIDE side, the bool
+// bytes: cut on 16 KiB of the bits a tile would be 128 KiB of bool and a
+// 4 MiB mask would occupy 32 workgroups.  Here a wave step is 8 KiB of bool
+// and 1 KiB of bits, a 256-thread workgroup trip is four steps, one per wave
+// (32 KiB and 4 KiB), workgroups loop tile += gridDim.x, at most 1024 of them
+// (the cap of the other checksum-carrying kernels, carried over, not
+// measured).
+//
+// Pack, one wave step:
+//
+//   - each lane issues 8 nontemporal 16-byte loads, source vector
+//     step * 512 + k * 64 + lane, coalesced, all before the first use;
+//   - a vector of 16 bool bytes becomes 16 bits in registers: per dword
+//     ((w * 0x01020408) >> 24) & 0xF, which brings bits 0, 8, 16 and 24 to
+//     bits 24 to 27 with no two partial products on one bit, exact when every
+//     byte is 0 or 1; w & 0xFEFEFEFE goes into `bad`;
+//   - the piece is written with ds_write_b16 at halfword k * 64 + lane of a
+//     wave-private 1 KiB LDS strip, its linear output position, consecutive
+//     across the lanes;
+//   - after narrow_strip_sync() each lane reads one b128 at lane * 16, sums it
+//     with checksum_add at its word index and stores it once, aligned and
+//     nontemporal.  Only lanes of one wave share a strip: no workgroup
+//     barrier in the loop.
+//
+// dst == nullptr is a probe through a grid-uniform branch: `bad` only, no
+// LDS, no stores.  Only source vectors wholly below numel are loaded whole,
+// the last numel % 16 bytes are read byte by byte into a zero vector, nothing
+// past numel is read and nothing past dst_bytes written; pad bits and pad
+// bytes come out zero because what they are made from is zero.
+//
+// Unpack, one wave step (no LDS: a halfword of bits is one wide vector, so
+// coalesced 2-byte loads already give every lane its own output vector):
+//
+//   - each lane issues 8 two-byte loads of halfword step * 512 + k * 64 + lane,
+//     128 contiguous bytes per instruction, all before the first use;
+//   - a halfword becomes 16 bytes in registers: per nibble
+//     (n * 0x00204081) & 0x01010101, which brings bits 0 to 3 to bits 0, 8, 16
+//     and 24, again without two partial products on one bit;
+//   - the vector is summed with checksum_add at its word index in the wide
+//     buffer and stored nontemporally at wide vector step * 512 + k * 64 +
+//     lane: 1 KiB contiguous per store instruction; with dst2 set (uniform for
+//     the grid) the same registers are stored there too, so the cached master
+//     and the electron's tensor come from one pass.
+//
+// The pad bits of the last byte and the pad bytes of the buffer may hold
+// anything: what they unpack to lies at or past numel and reaches neither a
+// store nor the sum.  The last partial wide vector is stored byte by byte and
+// summed with its missing bytes as zero, which is csp_checksum_dev of numel
+// bytes.  Nothing is multiplied by anything but a constant: no MFMA.
+static const int kBoolStepVecs = 64;  // vectors of bits of one wave step, 1 KiB
+static const int kBoolRatio = 8;      // bool vectors per vector of bits
+static const size_t kBoolStepWide = size_t(kBoolStepVecs) * kBoolRatio;  // 512 vectors, 8 KiB
+static const int kBoolStepsPerTrip = 4;  // one per wave of the workgroup
+static const uint64_t kBoolMaxBytes = uint64_t(16) << 30;
+
+// 16 bool bytes as 16 bits; `bad` gets the bits that make a byte neither 0 nor 1
+__device__ __forceinline__ unsigned short bool_pack_vec(u32x4 v, unsigned int& bad) {
+    bad |= (v[0] | v[1] | v[2] | v[3]) & 0xFEFEFEFEu;
+    unsigned int bits = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bits |= (((v[j] * 0x01020408u) >> 24) & 0xFu) << (4 * j);
+    return (unsigned short)bits;
+}
+
+// 16 bits as 16 bool bytes
+__device__ __forceinline__ u32x4 bool_unpack_half(unsigned int h) {
+    u32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (((h >> (4 * j)) & 0xFu) * 0x00204081u) & 0x01010101u;
+    return o;
+}
+
+// the `rem` (1..15) bytes that are left of the bool source's last, partial vector
+__device__ __forceinline__ u32x4 bool_load_tail(const u32x4* p, unsigned int rem) {
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(p);
+    u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (unsigned int j = 0; j < 15; ++j)
+        if (j < rem) v[j / 4] |= (unsigned int)b[j] << (8 * (j % 4));
+    return v;
+}
+
+// nsv: source vectors wholly below numel; rem: bytes of the partial one after
+// them; nov: vectors of bits, the zero-padded last one included
+__global__ __launch_bounds__(256) void csp_bool_pack_checksum_kernel(
+    const u32x4* __restrict__ src, size_t nsv, unsigned int rem, u32x4* __restrict__ dst,
+    size_t nov, size_t ntiles, unsigned long long* __restrict__ out) {
+    __shared__ u32x4 strip[kBoolStepsPerTrip][kBoolStepVecs];
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = threadIdx.x >> 6;
+    unsigned long long s0 = 0, t = 0;
+    unsigned int bad = 0;
+    for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        // the step depends on the tile and the wave alone: every branch on it
+        // is wave-uniform, and all 64 lanes reach the strip together
+        const size_t step = tile * kBoolStepsPerTrip + wave;
+        if (step * kBoolStepVecs >= nov) break;  // the last tile's unused steps
+        const size_t sv0 = step * kBoolStepWide + lane;
+        u32x4 v[kBoolRatio];
+        if ((step + 1) * kBoolStepWide <= nsv) {
+#pragma unroll
+            for (int k = 0; k < kBoolRatio; ++k)
+                v[k] = __builtin_nontemporal_load(&src[sv0 + k * kBoolStepVecs]);
+        } else {  // the step that holds the source's end
+#pragma unroll
+            for (int k = 0; k < kBoolRatio; ++k) {
+                const size_t sv = sv0 + k * kBoolStepVecs;
+                v[k] = u32x4{0u, 0u, 0u, 0u};
+                if (sv < nsv) v[k] = __builtin_nontemporal_load(&src[sv]);
+                else if (sv == nsv && rem != 0) v[k] = bool_load_tail(src + nsv, rem);
+            }
+        }
+        if (dst == nullptr) {  // probe: uniform for the whole grid
+#pragma unroll
+            for (int k = 0; k < kBoolRatio; ++k) (void)bool_pack_vec(v[k], bad);
+            continue;
+        }
+        unsigned short* pieces = reinterpret_cast<unsigned short*>(&strip[wave][0]);
+#pragma unroll
+        for (int k = 0; k < kBoolRatio; ++k)
+            pieces[k * kBoolStepVecs + lane] = bool_pack_vec(v[k], bad);
+        narrow_strip_sync();
+        const size_t ov = step * kBoolStepVecs + lane;
+        const u32x4 o = strip[wave][lane];
+        if (ov < nov) {
+            __builtin_nontemporal_store(o, &dst[ov]);
+            checksum_add(s0, t, o, (unsigned int)(ov * 4));
+        }
+        narrow_strip_sync();  // the next trip overwrites the strip
+    }
+    unsigned long long s1 = t + s0;
+    unsigned long long b = bad;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+        b |= __shfl_down(b, off, 64);
+    }
+    __shared__ unsigned long long part[3][4];
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+        part[2][wave] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (dst != nullptr) {
+            atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+            atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+        }
+        atomicOr(&out[2], part[2][0] | part[2][1] | part[2][2] | part[2][3]);
+    }
+}
+
+// one bool vector to a destination: whole below nwv, its first `rem` bytes at nwv
+__device__ __forceinline__ void bool_unpack_store(u32x4* __restrict__ dst, size_t wv, size_t nwv,
+                                                  unsigned int rem, u32x4 o) {
+    if (wv < nwv) {
+        __builtin_nontemporal_store(o, &dst[wv]);
+    } else {
+        unsigned char* b = reinterpret_cast<unsigned char*>(dst + nwv);
+#pragma unroll
+        for (unsigned int j = 0; j < 15; ++j)
+            if (j < rem) b[j] = (unsigned char)(o[j / 4] >> (8 * (j % 4)));
+    }
+}
+
+// src: the bits as halfwords; nwv: bool vectors wholly below numel; rem: bytes
+// of the partial one after them.  Halfword h holds the bits of bool vector h,
+// and every halfword below nwv + (rem != 0) lies inside the rounded buffer.
+__global__ __launch_bounds__(256) void csp_bool_unpack_checksum_kernel(
+    const unsigned short* __restrict__ src, u32x4* __restrict__ dst, u32x4* __restrict__ dst2,
+    size_t nwv, unsigned int rem, size_t ntiles, unsigned long long* __restrict__ out) {
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = threadIdx.x >> 6;
+    const size_t nv = nwv + (rem != 0 ? 1 : 0);
+    unsigned long long s0 = 0, t = 0;
+    for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const size_t step = tile * kBoolStepsPerTrip + wave;
+        if (step * kBoolStepWide >= nv) break;  // the last tile's unused steps
+        const size_t h0 = step * kBoolStepWide + lane;
+        unsigned int h[kBoolRatio];
+        if ((step + 1) * kBoolStepWide <= nv) {
+#pragma unroll
+            for (int k = 0; k < kBoolRatio; ++k)
+                h[k] = __builtin_nontemporal_load(&src[h0 + k * kBoolStepVecs]);
+        } else {  // the step that holds the input's end
+#pragma unroll
+            for (int k = 0; k < kBoolRatio; ++k) {
+                const size_t hv = h0 + k * kBoolStepVecs;
+                h[k] = 0u;
+                if (hv < nv) h[k] = __builtin_nontemporal_load(&src[hv]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kBoolRatio; ++k) {
+            const size_t wv = h0 + k * kBoolStepVecs;
+            if (wv >= nv) continue;
+            u32x4 o = bool_unpack_half(h[k]);
+            if (wv == nwv) {  // the partial vector: pad bits do not count
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int keep = (int)rem - 4 * q;
+                    if (keep <= 0) o[q] = 0u;
+                    else if (keep < 4) o[q] &= (1u << (8 * keep)) - 1u;
+                }
+            }
+            checksum_add(s0, t, o, (unsigned int)(wv * 4));
+            bool_unpack_store(dst, wv, nwv, rem, o);
+            if (dst2 != nullptr) bool_unpack_store(dst2, wv, nwv, rem, o);
+        }
+    }
+    unsigned long long s1 = t + s0;
+
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    __shared__ unsigned long long part[2][4];
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&out[1], part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+static const size_t kBoolGridCapDefault = 1024;
+static size_t g_bool_pack_grid_cap = kBoolGridCapDefault;
+static size_t g_bool_unpack_grid_cap = kBoolGridCapDefault;
+
+// Tools only: the grid cap of the next csp_bool_pack_checksum_dev calls (0
+// restores the default).  Returns the cap in effect.  With a cap of 1, 2 or 3
+// workgroups a few trips' worth of data makes every workgroup take several.
+extern "C" size_t csp_bool_pack_checksum_grid_cap(size_t cap) {
+    g_bool_pack_grid_cap = cap ? std::min(cap, size_t(65536)) : kBoolGridCapDefault;
+    return g_bool_pack_grid_cap;
+}
+
+// The same for csp_bool_unpack_checksum_dev.
+extern "C" size_t csp_bool_unpack_checksum_grid_cap(size_t cap) {
+    g_bool_unpack_grid_cap = cap ? std::min(cap, size_t(65536)) : kBoolGridCapDefault;
+    return g_bool_unpack_grid_cap;
+}
+
+static bool bool_ranges_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) {
+    return a + na < a || b + nb < b || (a < b + nb && b < a + na);
+}
+
+// Test the numel bool bytes at device pointer src for the "bits" form and put
+// into *bad the OR of byte & 0xFE over all of them: 0 iff every byte is 0 or 1.
+//
+//   - dst == nullptr: a probe.  Nothing is stored, dst_bytes is not looked
+//     at, sums is zero;
+//   - dst set: the bits are also written to dst, element i as bit i % 8 of
+//     byte i / 8, zero padded to dst_bytes = ceil(numel / 8) rounded up to 16,
+//     whatever the verdict.  With *bad == 0, sums equals
+//     csp_checksum_dev(dst, dst_bytes); otherwise dst and sums mean nothing.
+//
+// Returns 0, or -1 with a message and nothing launched for a null sums or bad,
+// a null src for numel > 0, a src or dst that is not 16-byte aligned, a wrong
+// dst_bytes, numel above 16 GiB or a dst that overlaps src; and for a HIP
+// failure.  numel == 0 returns 0 with zero sums and *bad == 0.  Runs on
+// copy_stream() and synchronises it before returning; a src written on another
+// stream must be complete first.  kernel_ms (optional): the kernel alone, from
+// events around the launch.
+extern "C" int csp_bool_pack_checksum_dev(const void* src, size_t numel, void* dst,
+                                          size_t dst_bytes, uint64_t sums[2], uint32_t* bad,
+                                          float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (sums == nullptr || bad == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_bool_pack_checksum_dev: null output pointer");
+        return -1;
+    }
+    sums[0] = sums[1] = 0;
+    *bad = 0;
+    if (numel == 0) return 0;
+    const uintptr_t s_addr = reinterpret_cast<uintptr_t>(src);
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dst);
+    if (s_addr == 0) {
+        snprintf(g_err, sizeof(g_err), "csp_bool_pack_checksum_dev: null src for %zu elements",
+                 numel);
+        return -1;
+    }
+    if (s_addr % 16 != 0 || d % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_bool_pack_checksum_dev: src %p and dst %p must be 16-byte aligned", src, dst);
+        return -1;
+    }
+    if (numel > kBoolMaxBytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_bool_pack_checksum_dev: %zu elements are above the 16 GiB bound", numel);
+        return -1;
+    }
+    const size_t want = ((numel + 7) / 8 + 15) / 16 * 16;
+    if (dst != nullptr) {
+        if (dst_bytes != want) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_bool_pack_checksum_dev: dst_bytes %zu, %zu elements need %zu", dst_bytes,
+                     numel, want);
+            return -1;
+        }
+        if (bool_ranges_overlap(s_addr, numel, d, want)) {
+            snprintf(g_err, sizeof(g_err),
+                     "csp_bool_pack_checksum_dev: %zu bytes at dst %p overlap %zu bytes at src %p",
+                     want, dst, numel, src);
+            return -1;
+        }
+    }
+
+    // two sums and the `bad` word per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static int acc_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (acc == nullptr || acc_device != device) {
+        if (acc) (void)hipFree(acc);
+        acc = nullptr;
+        HIP_TRY(hipMalloc(&acc, 3 * sizeof(unsigned long long)));
+        acc_device = device;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define BOOLPACK_TRY(expr)                                         \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    BOOLPACK_TRY(hipMemsetAsync(acc, 0, 3 * sizeof(unsigned long long), s));
+    const size_t nsv = numel / 16;
+    const unsigned int rem = (unsigned int)(numel % 16);
+    const size_t nov = want / 16;
+    const size_t trip = size_t(kBoolStepsPerTrip) * kBoolStepVecs;
+    const size_t ntiles = (nov + trip - 1) / trip;
+    const size_t blocks = std::min(ntiles, g_bool_pack_grid_cap);
+    if (t0) BOOLPACK_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_bool_pack_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       static_cast<const u32x4*>(src), nsv, rem, static_cast<u32x4*>(dst), nov,
+                       ntiles, acc);
+    BOOLPACK_TRY(hipGetLastError());
+    if (t1) BOOLPACK_TRY(hipEventRecord(t1, s));
+    unsigned long long host[3] = {0, 0, 0};
+    BOOLPACK_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    BOOLPACK_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) BOOLPACK_TRY(hipEventElapsedTime(kernel_ms, t0, t1));
+#undef BOOLPACK_TRY
+    sums[0] = host[0];
+    sums[1] = host[1];
+    // the kernel ORs dwords: fold their four byte lanes into byte & 0xFE
+    const uint32_t lanes = (uint32_t)host[2];
+    *bad = (lanes | lanes >> 8 | lanes >> 16 | lanes >> 24) & 0xFEu;
+    return done(0);
+}
+
+// Unpack the numel elements held as bits at device pointer src (element i in
+// bit i % 8 of byte i / 8) into bool bytes, 0 or 1 each, at dst and, when dst2
+// is set, at dst2 as well, and put csp_checksum_dev(dst, numel) into sums, all
+// in one kernel launch.  src must be readable up to ceil(numel / 8) rounded up
+// to 16; the pad bits and pad bytes may hold anything.  dst and dst2 are numel
+// bytes, and nothing past that is written.
+//
+// Returns 0, or -1 with a message and nothing launched for a null sums, src or
+// dst, a src, dst or dst2 that is not 16-byte aligned, numel above 16 GiB or
+// any overlap among the three ranges (src taken with its rounded extent); and
+// for a HIP failure.  numel == 0 returns 0 with zero sums.  Runs on
+// copy_stream(), so it is ordered after the copies that csp_h2d_stream_fd
+// issued, and synchronises that stream before returning.  kernel_ms
+// (optional): the kernel alone, from events around the launch.
+extern "C" int csp_bool_unpack_checksum_dev(const void* src, size_t numel, void* dst, void* dst2,
+                                            uint64_t sums[2], float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (sums == nullptr) {
+        snprintf(g_err, sizeof(g_err), "csp_bool_unpack_checksum_dev: null output pointer");
+        return -1;
+    }
+    sums[0] = sums[1] = 0;
+    if (numel == 0) return 0;
+    const uintptr_t s_addr = reinterpret_cast<uintptr_t>(src);
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t d2 = reinterpret_cast<uintptr_t>(dst2);
+    if (s_addr == 0 || d == 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_bool_unpack_checksum_dev: null src or dst for %zu elements", numel);
+        return -1;
+    }
+    if (s_addr % 16 != 0 || d % 16 != 0 || d2 % 16 != 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_bool_unpack_checksum_dev: src %p, dst %p and dst2 %p must be 16-byte aligned",
+                 src, dst, dst2);
+        return -1;
+    }
+    if (numel > kBoolMaxBytes) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_bool_unpack_checksum_dev: %zu elements are above the 16 GiB bound", numel);
+        return -1;
+    }
+    const size_t bits_bytes = ((numel + 7) / 8 + 15) / 16 * 16;
+    if (bool_ranges_overlap(s_addr, bits_bytes, d, numel) ||
+        (d2 != 0 && (bool_ranges_overlap(s_addr, bits_bytes, d2, numel) ||
+                     bool_ranges_overlap(d, numel, d2, numel)))) {
+        snprintf(g_err, sizeof(g_err),
+                 "csp_bool_unpack_checksum_dev: %zu bytes at src %p, %zu bytes at dst %p and at "
+                 "dst2 %p overlap",
+                 bits_bytes, src, numel, dst, dst2);
+        return -1;
+    }
+
+    // one accumulator pair per process, one call at a time
+    std::lock_guard<std::mutex> lock(g_checksum_mu);
+    static unsigned long long* acc = nullptr;
+    static int acc_device = -1;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (acc == nullptr || acc_device != device) {
+        if (acc) (void)hipFree(acc);
+        acc = nullptr;
+        HIP_TRY(hipMalloc(&acc, 2 * sizeof(unsigned long long)));
+        acc_device = device;
+    }
+    hipStream_t s = copy_stream();
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&t0));
+        hipError_t e = hipEventCreate(&t1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(t0);
+            return set_err("hipEventCreate", e);
+        }
+    }
+    auto done = [&](int rc) {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        return rc;
+    };
+#define BOOLUNPACK_TRY(expr)                                       \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return done(set_err(#expr, _e));     \
+    } while (0)
+    BOOLUNPACK_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+    const size_t nwv = numel / 16;
+    const unsigned int rem = (unsigned int)(numel % 16);
+    const size_t nv = nwv + (rem != 0 ? 1 : 0);
+    const size_t trip = size_t(kBoolStepsPerTrip) * kBoolStepWide;
+    const size_t ntiles = (nv + trip - 1) / trip;
+    const size_t blocks = std::min(ntiles, g_bool_unpack_grid_cap);
+    if (t0) BOOLUNPACK_TRY(hipEventRecord(t0, s));
+    hipLaunchKernelGGL(csp_bool_unpack_checksum_kernel, dim3((unsigned int)blocks), dim3(256), 0, s,
+                       static_cast<const unsigned short*>(src), static_cast<u32x4*>(dst),
+                       static_cast<u32x4*>(dst2), nwv, rem, ntiles, acc);
+    BOOLUNPACK_TRY(hipGetLastError());
+    if (t1) BOOLUNPACK_TRY(hipEventRecord(t1, s));
+    unsigned long long host[2] = {0, 0};
+    BOOLUNPACK_TRY(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+    BOOLUNPACK_TRY(hipStreamSynchronize(s));
+    if (kernel_ms) BOOLUNPACK_TRY(hipEventElapsedTime(kernel_ms, t0, t1));
+#undef BOOLUNPACK_TRY
+    sums[0] = host[0];
+    sums[1] = host[1];
+    return done(0);
+}
+
 // On-box variant exploration for the HBM sweep (tools only; the probe
 // uses g_sweep_variant).  Returns measured GB/s via *gbps.
 extern "C" int csp_hbm_bench(int device, int variant, size_t bytes, int reps,

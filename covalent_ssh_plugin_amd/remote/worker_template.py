@@ -44,7 +44,10 @@ Protocol (all frames: 8-byte big-endian length + payload):
              widens it into the tensor (with "store": into the master and
              the tensor) and yields the checksum of the wide bytes, which
              is what "sum" announces; meta["arg_staging"] then counts
-             "widened", "wire_bytes" and "widen_ms".
+             "widened", "wire_bytes" and "widen_ms".  A bool tensor's
+             "wire" is "bits": element i in bit i % 8 of byte i // 8,
+             ceil(numel / 8) bytes, unpacked by ONE
+             csp_bool_unpack_checksum_dev call in the same way.
              With the executor option pack_tensor_args the small tensor
              arguments of one electron share ONE entry {"device": true,
              "packed": [{dtype, shape, offset, nbytes}, ...], "nbytes":
@@ -146,8 +149,10 @@ Protocol (all frames: 8-byte big-endian length + payload):
              meta["staging"] counts "narrowed", "narrow_saved_bytes" and
              "narrow_ms" (the calls and the buffer, the inexact ones too),
              and a tensor that is not exact or is refused travels whole
-             with the reason in "narrow_fallback".  With
-             pack_tensor_results as well, a packed arena that is not retained
+             with the reason in "narrow_fallback".  A bool tensor takes ONE
+             csp_bool_pack_checksum_dev call and leaves as "wire": "bits",
+             one bit per element, unless a storage byte is neither 0 nor 1.
+             With pack_tensor_results as well, a packed arena that is not retained
              and holds no strided tensor is narrowed too: ONE
              csp_pack_narrow_probe_dev call tests its contiguous, 16-byte
              aligned float32, float64, int32 and int64 tensors, and ONE
@@ -229,6 +234,12 @@ WIDEN_PAIRS = {
     ("uint8", "int64"): (6, 3, 1, 8), ("int16", "int32"): (5, 2, 2, 4),
     ("uint8", "int32"): (6, 2, 1, 4),
 }
+# A torch.bool tensor travels one bit per element under both options: element
+# i is bit i % 8 of byte i // 8.  csp_bool_pack_checksum_dev makes a result's
+# bits, csp_bool_unpack_checksum_dev an argument's bytes.  bool is kept out of
+# NARROW_TARGETS and WIDEN_PAIRS: the packed-arena code reads those tables.
+BOOL_WIRE = "bits"
+BOOL_PAIR = (None, None, 0, 1)  # _widen_pair's entry for (BOOL_WIRE, "bool")
 # Fork-isolation mode: the worker is a warm ZYGOTE (python + cloudpickle
 # imported, HIP **not** initialized — initializing HIP pre-fork would
 # break the children) and every electron executes in a freshly forked
@@ -460,6 +471,27 @@ def _load_gpu_lib():
             ctypes.c_size_t,
             ctypes.c_int,
             ctypes.c_int,
+            ctypes.c_void_p,
+            ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_float),
+        ]
+    if NARROW_RESULTS and hasattr(lib, "csp_bool_pack_checksum_dev"):
+        lib.csp_bool_pack_checksum_dev.restype = ctypes.c_int
+        lib.csp_bool_pack_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.c_void_p,
+            ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint32),
+            ctypes.POINTER(ctypes.c_float),
+        ]
+    if hasattr(lib, "csp_bool_unpack_checksum_dev"):
+        lib.csp_bool_unpack_checksum_dev.restype = ctypes.c_int
+        lib.csp_bool_unpack_checksum_dev.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_size_t,
             ctypes.c_void_p,
             ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_uint64),
@@ -731,6 +763,47 @@ def _narrow(lib, t, stats):
         stats.get("narrow_saved_bytes", 0) + t.numel() * t.element_size() - wire
     )
     return flat, wire, name, sums
+
+
+def _narrow_bool(lib, t, stats):
+    """_narrow for a contiguous torch.bool CUDA tensor: ONE
+    csp_bool_pack_checksum_dev call packs eight elements into a byte straight
+    into the buffer and tests every storage byte for 0 or 1; there is one
+    target, BOOL_WIRE, so no probe.  A byte that is neither (a uint8 tensor
+    viewed as bool) sends the tensor whole."""
+    import ctypes
+
+    import torch
+
+    t0 = time.monotonic()
+    try:
+        if not hasattr(lib, "csp_bool_pack_checksum_dev"):
+            raise RuntimeError("the GPU library has no csp_bool_pack_checksum_dev")
+        wire = (t.numel() + 7) // 8
+        total = (wire + 15) // 16 * 16
+        flat = torch.empty(total, dtype=torch.uint8, device="cuda")
+        sums = (ctypes.c_uint64 * 2)()
+        bad = ctypes.c_uint32()
+        rc = lib.csp_bool_pack_checksum_dev(
+            ctypes.c_void_p(t.data_ptr()), t.numel(), ctypes.c_void_p(flat.data_ptr()), total,
+            sums, ctypes.byref(bad), None,
+        )
+        if rc != 0:
+            raise RuntimeError(
+                "csp_bool_pack_checksum_dev failed (rc=%d): %s"
+                % (rc, lib.csp_last_error().decode(errors="replace"))
+            )
+        if bad.value:
+            raise ValueError("bool storage bytes other than 0 and 1 are not exact as bits")
+    except Exception as e:  # noqa: BLE001
+        stats["narrow_fallback"] = repr(e)[:500]
+        return None
+    finally:
+        stats["narrow_ms"] = round(
+            stats.get("narrow_ms", 0.0) + (time.monotonic() - t0) * 1000, 3)
+    stats["narrowed"] = stats.get("narrowed", 0) + 1
+    stats["narrow_saved_bytes"] = stats.get("narrow_saved_bytes", 0) + t.numel() - wire
+    return flat, wire, BOOL_WIRE, [int(sums[0]), int(sums[1])]
 
 
 def _has_pack_narrow(lib):
@@ -1260,10 +1333,10 @@ def _stage_result(result, stats, buffers, buffer_meta, retain=None):
             if (
                 NARROW_RESULTS
                 and src_t is t
-                and str(t.dtype).replace("torch.", "") in NARROW_TARGETS
+                and (str(t.dtype).replace("torch.", "") in NARROW_TARGETS or t.dtype == torch.bool)
                 and t.data_ptr() % 16 == 0
             ):
-                narrowed = _narrow(lib, t, stats)
+                narrowed = (_narrow_bool if t.dtype == torch.bool else _narrow)(lib, t, stats)
                 if narrowed is not None:
                     flat, wire, name, sums = narrowed
                     stats["pinned_tensors"] += 1
@@ -1608,6 +1681,13 @@ def _device_arg_from_cache(lib, index, info, dtype, nbytes, key, stage, report):
 def _widen_pair(lib, index, info):
     """The WIDEN_PAIRS entry of an argument entry that carries ``"wire"``;
     RuntimeError for a pair or a library that cannot widen it."""
+    if (info["wire"], info["dtype"]) == (BOOL_WIRE, "bool"):
+        if not hasattr(lib, "csp_bool_unpack_checksum_dev"):
+            raise RuntimeError(
+                "argument buffer %d arrived as bits and the GPU library has no "
+                "csp_bool_unpack_checksum_dev" % index
+            )
+        return BOOL_PAIR
     pair = WIDEN_PAIRS.get((info["wire"], info["dtype"]))
     if pair is None:
         raise RuntimeError(
@@ -1622,6 +1702,11 @@ def _widen_pair(lib, index, info):
     return pair
 
 
+def _wire_bytes(pair, numel):
+    """The bytes of ``numel`` elements on the wire for a _widen_pair entry."""
+    return (numel + 7) // 8 if pair is BOOL_PAIR else numel * pair[2]
+
+
 def _widen_device_arg(lib, index, pair, narrow, numel, dst, dst2, stage):
     """ONE csp_widen_checksum_dev call: the ``numel`` narrow elements in the
     uint8 CUDA buffer ``narrow`` widened into ``dst`` and, when given,
@@ -1630,19 +1715,26 @@ def _widen_device_arg(lib, index, pair, narrow, numel, dst, dst2, stage):
 
     out = (ctypes.c_uint64 * 2)()
     ms = ctypes.c_float()
-    rc = lib.csp_widen_checksum_dev(
-        ctypes.c_void_p(narrow.data_ptr()), numel, pair[0], pair[1],
-        ctypes.c_void_p(dst.data_ptr()),
-        ctypes.c_void_p(dst2.data_ptr() if dst2 is not None else None),
-        out, ctypes.byref(ms),
-    )
+    second = ctypes.c_void_p(dst2.data_ptr() if dst2 is not None else None)
+    if pair is BOOL_PAIR:
+        name = "csp_bool_unpack_checksum_dev"
+        rc = lib.csp_bool_unpack_checksum_dev(
+            ctypes.c_void_p(narrow.data_ptr()), numel, ctypes.c_void_p(dst.data_ptr()), second,
+            out, ctypes.byref(ms),
+        )
+    else:
+        name = "csp_widen_checksum_dev"
+        rc = lib.csp_widen_checksum_dev(
+            ctypes.c_void_p(narrow.data_ptr()), numel, pair[0], pair[1],
+            ctypes.c_void_p(dst.data_ptr()), second, out, ctypes.byref(ms),
+        )
     if rc != 0:
         raise RuntimeError(
-            "argument buffer %d: csp_widen_checksum_dev failed: %s"
-            % (index, lib.csp_last_error().decode(errors="replace"))
+            "argument buffer %d: %s failed: %s"
+            % (index, name, lib.csp_last_error().decode(errors="replace"))
         )
     stage["widened"] = stage.get("widened", 0) + 1
-    stage["wire_bytes"] = stage.get("wire_bytes", 0) + numel * pair[2]
+    stage["wire_bytes"] = stage.get("wire_bytes", 0) + _wire_bytes(pair, numel)
     stage["widen_ms"] = stage.get("widen_ms", 0.0) + ms.value
     return [int(out[0]), int(out[1])]
 
@@ -1695,7 +1787,7 @@ def _receive_device_arg(index, info, stage, report):
             if _read_frame(0) is None:  # its length is unknown here: the Python reader
                 os._exit(4)
             raise
-        frame_bytes = nbytes // pair[3] * pair[2]
+        frame_bytes = _wire_bytes(pair, nbytes // pair[3])
     key = None
     master = None
     if cache.get("store") and "sum" in info and nbytes:
@@ -2495,7 +2587,7 @@ def _device_args_in_child(frames, meta_list, stage):
             # the same single widening call as in persistent mode
             pair = _widen_pair(lib, i, info)
             tensor = torch.empty(info["shape"], dtype=dtype, device="cuda")
-            wire_bytes = tensor.numel() * pair[2]
+            wire_bytes = _wire_bytes(pair, tensor.numel())
             if len(frames[i]) != wire_bytes:
                 raise RuntimeError(
                     "argument buffer %d: the narrowed frame has %d bytes, its "

@@ -227,8 +227,15 @@ def narrow_arg(view, dtype: str, chunk_bytes: int = ARG_CACHE_CHUNK,
     then a narrow pass at the tightest fitting target; a float takes one pass,
     and its buffer is dropped when ``bad`` is set.  ``stats`` gets
     ``arg_narrowed``, ``arg_narrow_saved_bytes`` and ``arg_narrow_ms`` (the
-    attempts that came out inexact included)."""
+    attempts that came out inexact included).
+
+    A ``bool`` tensor has one target, ``"bits"``: one ``native_io.bool_pack``
+    pass per chunk (chunks start on a multiple of 8 elements), and the buffer
+    is dropped when a storage byte is neither 0 nor 1 (a ``uint8`` viewed as
+    bool); the worker unpacks with ``csp_bool_unpack_checksum_dev``."""
     lib = native_io.load()
+    if dtype == "bool":
+        return _narrow_bool_arg(lib, view, chunk_bytes, threads, stats)
     targets = native_io.NARROW_TARGETS.get(dtype)
     if lib is None or not hasattr(lib, "csp_io_narrow") or not targets:
         return None
@@ -269,6 +276,31 @@ def narrow_arg(view, dtype: str, chunk_bytes: int = ARG_CACHE_CHUNK,
                 stats.get("arg_narrow_saved_bytes", 0) + nbytes - len(out)
             )
     return None if wire is None else (wire, out)
+
+
+def _narrow_bool_arg(lib, view, chunk_bytes, threads, stats):
+    """The bool branch of :func:`narrow_arg`."""
+    if lib is None or not hasattr(lib, "csp_io_bool_pack"):
+        return None
+    started = time.perf_counter()
+    numel = memoryview(view).nbytes
+    out = bytearray(native_io.bool_bits_bytes(numel))
+    bad = 0
+    for b in _map(
+        lambda p: native_io.bool_pack(view, p[1], out, p[0], p[0] // 8),
+        _chunks(numel, max(8, chunk_bytes // 8 * 8)), threads,
+    ):
+        bad |= b
+    if stats is not None:
+        stats["arg_narrow_ms"] = (
+            stats.get("arg_narrow_ms", 0.0) + (time.perf_counter() - started) * 1e3
+        )
+        if bad == 0:
+            stats["arg_narrowed"] = stats.get("arg_narrowed", 0) + 1
+            stats["arg_narrow_saved_bytes"] = (
+                stats.get("arg_narrow_saved_bytes", 0) + numel - len(out)
+            )
+    return None if bad else (native_io.BOOL_WIRE, out)
 
 
 _key_memo: Dict[int, tuple] = {}  # id(tensor) -> (weakref, guard, key)
@@ -653,7 +685,7 @@ def extract_arg_buffers(
                 if cacheable:
                     info["cache"] = {"key": tensor_content_key(t, view)}
                 if narrow and nbytes >= max(1, threshold) and (
-                    info["dtype"] in native_io.NARROW_TARGETS
+                    info["dtype"] in native_io.NARROW_TARGETS or info["dtype"] == "bool"
                 ):
                     if cacheable:  # decided when the bytes travel, not for a ref
                         info["cache"]["narrow"] = True
@@ -785,9 +817,20 @@ def widen_result(data, info):
     only what this widening gives back bit for bit: bfloat16 to float32 appends
     16 zero bits, float32 to float64 is exact for the zeros, normals,
     infinities and quiet NaNs it lets through, and integers are sign- or
-    zero-extended.  The result owns new memory."""
+    zero-extended.  A ``"bits"`` buffer holds a bool tensor one bit per element,
+    element ``i`` in bit ``i % 8`` of byte ``i // 8``; the worker sends it only
+    when every storage byte was 0 or 1.  The result owns new memory."""
     import torch
 
+    if info["wire"] == native_io.BOOL_WIRE:
+        import numpy as np
+
+        numel = 1
+        for dim in info["shape"]:
+            numel *= int(dim)
+        bits = np.frombuffer(data, dtype=np.uint8, count=native_io.bool_bits_bytes(numel))
+        wide = np.unpackbits(bits, bitorder="little", count=numel)
+        return torch.from_numpy(wide).view(torch.bool).reshape(info["shape"])
     narrow = torch.frombuffer(data, dtype=getattr(torch, info["wire"]))
     return narrow.reshape(info["shape"]).to(getattr(torch, info["dtype"]))
 

@@ -209,6 +209,8 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # worker tests every element, narrows and checksums; the dispatcher
     # verifies the narrow bytes and widens them back, bit for bit.  A tensor
     # with one element that does not fit travels whole, as without the option.
+    # A bool tensor travels as bits, one per element, unless a storage byte is
+    # neither 0 nor 1.
     "narrow_tensor_results": False,
     # The argument side of it (needs device_tensor_args): a large contiguous
     # CPU tensor argument of float32, float64, int32 or int64 on the
@@ -218,7 +220,8 @@ _EXECUTOR_PLUGIN_DEFAULTS = {
     # float32 values as float32).  The worker lands the narrow bytes in HBM
     # and one kernel launch widens them, fills the cached master as well and
     # yields the checksum announced for the tensor's own bytes.  A tensor with
-    # one element that does not fit travels whole, as without the option.
+    # one element that does not fit travels whole, as without the option.  A
+    # bool tensor travels as bits and is unpacked in HBM the same way.
     "narrow_tensor_args": False,
     "cpu_workers": 4,  # worker-set size when no GPU policy is active
     # Sample HBM occupancy (hipMemGetInfo) into the task meta every Nth

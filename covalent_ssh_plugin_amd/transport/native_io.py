@@ -74,6 +74,11 @@ def load(path: str = "") -> Optional[ctypes.CDLL]:
             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_uint64),
         ]
+    if hasattr(lib, "csp_io_bool_pack"):  # a library built before the "bits" wire format
+        lib.csp_io_bool_pack.restype = ctypes.c_int
+        lib.csp_io_bool_pack.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+        ]
     _lib = lib
     return lib
 
@@ -208,6 +213,47 @@ def narrow(src, numel: int, src_kind: str, dst_kind: str, dst=None, src_offset: 
     del keep, out_keep
     if rc != 0:
         raise ValueError(f"no narrowing from {src_kind} to {dst_kind}")
+    return int(bad.value)
+
+
+# the wire name of a bool tensor sent one bit per element; it is no entry of
+# NARROW_TARGETS on purpose: the packed-arena code tests ``dtype in
+# NARROW_TARGETS`` and must not pick up bool segments
+BOOL_WIRE = "bits"
+
+
+def bool_bits_bytes(numel: int) -> int:
+    """Bytes of ``numel`` bool elements on the wire as ``"bits"``."""
+    return (numel + 7) // 8
+
+
+def bool_pack(src, numel: int, dst=None, src_offset: int = 0, dst_offset: int = 0) -> int:
+    """One pass of ``csp_io_bool_pack`` over the ``numel`` bool bytes at byte
+    ``src_offset`` of ``src``; returns the ``bad`` word of that piece, the OR of
+    ``byte & 0xFE`` (0: every byte is 0 or 1 and the bits give it back).  With
+    ``dst`` (a writable buffer) element ``i`` is written as bit ``i % 8`` of
+    byte ``dst_offset + i // 8`` (``numpy.packbits(bitorder="little")``),
+    whatever the verdict.  A piece of a larger tensor starts on a multiple of 8
+    elements.  ctypes drops the GIL for the call."""
+    lib = load()
+    if lib is None or not hasattr(lib, "csp_io_bool_pack"):
+        raise RuntimeError(f"{_LIB_NAME} is not built")
+    window = memoryview(src).cast("B")[src_offset : src_offset + numel]
+    if window.nbytes != numel:
+        raise ValueError("range outside the buffer")
+    if window.readonly:
+        keep = source = bytes(window)  # ctypes cannot borrow a read-only buffer
+    else:
+        keep = (ctypes.c_char * numel).from_buffer(window) if numel else None
+        source = ctypes.addressof(keep) if numel else None
+    out_addr, out_keep = (None, None)
+    if dst is not None:
+        out_addr, out_keep = _address(dst, dst_offset, bool_bits_bytes(numel))
+    bad = ctypes.c_uint64(0)
+    rc = lib.csp_io_bool_pack(source, numel, out_addr or None, ctypes.byref(bad))
+    del keep, out_keep
+    if rc != 0:
+        raise ValueError("csp_io_bool_pack refused the call")
     return int(bad.value)
 
 
